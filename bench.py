@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the MoPA hot path on MI355X (contract: see the task statement / DESIGN.md section "Measurement").
 
-    python bench.py --gpus N --steps K --warmup W [--workload 3d|joint|mopa] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--workload 3d|joint|mopa|kitti] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step` = milliseconds per timed step).
+`--full` adds everything else the line can carry, each measured after the timed region or taken from committed profiles: the
+roofline objects (HIP-event brackets on every 5th timed step, the merged 3D pass alone), `value_with_host_inputs`,
+`value_two_calls_per_domain`, `hbm_GB_per_step`, `config.gradient_error_vs_fp64` and the CPU baseline (`--no-cpu-baseline` skips it).
+`--dump-outputs DIR` writes what the last timed step computed -- its loss parts, every floating-point output of every forward call
+of both networks, the parameters after its Adam update and its gradients -- as DIR/<name>.npy (float32; an array of more than ~1 M
+elements as a fixed, seeded sample of its elements; 64 MB at most in all).  The inputs are the same from run to run for the same
+arguments, so two builds can be compared output for output.
 
 `--gpus N` with N > 1, started as a plain process (no RANK / WORLD_SIZE in the environment), launches N ranks itself:
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`, one rank
@@ -12,7 +21,7 @@ One "step" = one training pass of the hot path over one batch of B synthetic nuS
 before the timed region.  value = scans/s over all ranks (weak scaling: per-GPU batch fixed).
 
 A/B switches (environment; the defaults are what the numbers in DESIGN.md were measured with):
-  MOPA_BENCH_EVENT_STRIDE=5   HIP-event brackets (roofline figures) on every n-th timed step; 0 = none, 1 = every step
+  MOPA_BENCH_EVENT_STRIDE=5   with --full: HIP-event brackets (roofline figures) on every n-th timed step; 0 = none, 1 = every step
   MOPA_BENCH_STEP_TIMES=1     per-step host clock + caching-allocator counters + cyclic-GC passes of the timed region on stderr
   MOPA_BENCH_TIMELINE=1       HIP-event marks on the streams (ends of the forwards / losses / backwards of both halves), mean offsets on stderr
   MOPA_BENCH_GC_FREEZE=0      skip mopa_amd.step.freeze_host_heap() after the warm-up (then one 70-100 ms full GC pass lands in
@@ -57,8 +66,69 @@ def parse():
                     help="joint = BASELINE configs[2] (default), 3d = configs[1], mopa = configs[3] per-GPU step, "
                          "kitti = configs[4] per-GPU step (A2D2->SemanticKITTI shape: 120,000-pt scans, 10 classes, joint 2D+3D)")
     ap.add_argument("--batch", type=int, default=None, help="scans per domain per GPU (default 8; 4 for mopa; 2 for kitti)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside `value`: rooflines, host-input / two-call variants, committed PMC figures, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together (npy headers included)
+DUMP_MAX_ELEMENTS = 1 << 20      # an array with more elements is written as a fixed sample of this many
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as <out_dir>/<name>.npy in float32.  An array of more than `cap`
+    elements is written as `cap` of them, flattened, in ascending index order; the indices are drawn without replacement by a
+    generator seeded with the element count, so every run and every build picks the same elements (and a flat parameter buffer
+    and its gradient buffer the same ones).  `cap` shares the byte budget evenly among the arrays.  Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = max(1, min(DUMP_MAX_ELEMENTS, (DUMP_BUDGET_BYTES - 256 * len(arrays)) // (4 * max(1, len(arrays)))))
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            rng = np.random.Generator(np.random.PCG64(t.numel()))
+            idx = np.sort(rng.choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = np.ascontiguousarray(t.float().cpu().numpy())
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs wrote {total} bytes"
+    return total
+
+
+class OutputCapture:
+    """--dump-outputs: forward hooks on the networks for ONE step (the last timed one), keeping a copy of every floating-point tensor
+    each forward call returns (out<2d|3d>_<call>_<key>), taken on the stream current at the call, i.e. the one that produced it."""
+
+    def __init__(self, named_models):
+        self.named_models = named_models   # [(tag, module)]
+        self.outputs = {}
+        self.handles = []
+
+    def arm(self):
+        for tag, m in self.named_models:
+            calls = [0]
+
+            def hook(_mod, _inp, out, tag=tag, calls=calls):
+                if isinstance(out, dict):
+                    for k, v in out.items():
+                        if torch.is_tensor(v) and v.is_floating_point():
+                            self.outputs[f"out{tag}_{calls[0]}_{k}"] = v.detach().clone()
+                calls[0] += 1
+
+            self.handles.append(m.register_forward_hook(hook))
+
+    def disarm(self):
+        for h in self.handles:
+            h.remove()
+        self.handles = []
 
 
 class ConvTimer:
@@ -440,6 +510,8 @@ def main():
     NC = shape["classes"]
     lam_src, lam_trg = (0.1, 0.01) if kitti else (1.0, 0.1)   # lambda_xm_src / _trg: a2d2_semantic_kitti yaml :54-55, nuscenes :56-57
     torch.manual_seed(1 + rank)
+    np.random.seed(1 + rank)   # the VGI's draws (global numpy generator, as the reference's): the same from run to run
+    full = args.full
     cfg = default_cfg(num_classes=NC, dual_head=True)
     model3d, _ = build_model_3d(cfg)
     model3d = model3d.to(dev).train()
@@ -513,32 +585,35 @@ def main():
             bt["vgi_proj"] = np.array([[1266.0, 800.0, 0, 0], [0, 450.0, -1266.0, 0], [0, 1, 0, 0]], np.float64)
         batches.append(bt)
 
-    # what an empty event bracket reads on this box (median of 100, idle stream): context for the launch times below
-    torch.cuda.synchronize()
-    _ev = []
-    for _ in range(100):
-        _s, _e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        _s.record(); _e.record(); _ev.append((_s, _e))
-    torch.cuda.synchronize()
-    bracket_overhead_us = round(sorted(a.elapsed_time(b) * 1e3 for a, b in _ev)[50], 2)
+    # what an empty event bracket reads on this box (median of 100, idle stream): context for the launch times below (--full)
+    bracket_overhead_us = None
+    if full:
+        torch.cuda.synchronize()
+        _ev = []
+        for _ in range(100):
+            _s, _e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            _s.record(); _e.record(); _ev.append((_s, _e))
+        torch.cuda.synchronize()
+        bracket_overhead_us = round(sorted(a.elapsed_time(b) * 1e3 for a, b in _ev)[50], 2)
     from mopa_amd import sparse3d as sparse3d_mod
     native_default = sparse3d_mod.NATIVE
     from mopa_amd import dense2d as dense2d_mod
     graph2d_default = dense2d_mod.GRAPH_2D
     native2d_default = dense2d_mod.NATIVE_2D
-    timer = ConvTimer()
-    timer.install()
+    timer = ConvTimer()       # (--full only: a plain run installs no brackets, and their summaries stay None)
     timer2d = Conv2dTimer()
-    if joint:
-        timer2d.install()
-    for b in batches:  # rule counts for the algorithmic-bytes model (one-off, outside the timed region)
-        g = Geometry3D(b["locs"], 7, 4096, dev)
-        for l in range(7):
-            timer.rules[(27, g.num_active[l], g.num_active[l])] = g.num_rules[l]
-        for l in range(6):
-            timer.rules[(8, g.num_active[l + 1], g.num_active[l])] = g.num_active[l]   # down / deconv-dgrad
-            timer.rules[(8, g.num_active[l], g.num_active[l + 1])] = g.num_active[l]   # up / conv-dgrad
-        del g
+    if full:
+        timer.install()
+        if joint:
+            timer2d.install()
+        for b in batches:  # rule counts for the algorithmic-bytes model (one-off, outside the timed region)
+            g = Geometry3D(b["locs"], 7, 4096, dev)
+            for l in range(7):
+                timer.rules[(27, g.num_active[l], g.num_active[l])] = g.num_rules[l]
+            for l in range(6):
+                timer.rules[(8, g.num_active[l + 1], g.num_active[l])] = g.num_active[l]   # down / deconv-dgrad
+                timer.rules[(8, g.num_active[l], g.num_active[l + 1])] = g.num_active[l]   # up / conv-dgrad
+            del g
 
     from mopa_amd.step import DualStream
     reorder = os.environ.get("MOPA_BENCH_REORDER", "1") != "0"
@@ -690,7 +765,7 @@ def main():
 
     mode = {"pair": pair_mode}   # (mutable: the two-calls-per-domain figure after the timed region switches it off)
     pair2d = pair_batch_of(batches[0], batches[1]) if pair_mode else None
-    if pair_mode and pair2d[1] is not None:   # rule counts of the joint geometry for the algorithmic-bytes model (as above)
+    if full and pair_mode and pair2d[1] is not None:   # rule counts of the joint geometry for the algorithmic-bytes model (as above)
         g = Geometry3D(pair2d[1]["x"][0], 7, 4096, dev, group_points=pair2d[1]["bn_group_points"])
         for l in range(7):
             timer.rules[(27, g.num_active[l], g.num_active[l])] = g.num_rules[l]
@@ -796,7 +871,7 @@ def main():
     # `value_with_host_inputs` beside `value` (which by contract has its inputs resident in HBM).
     host_batches = None
     shared_gpu = multi and dist.get_backend() != "nccl"   # plumbing mode: several ranks on one device, keep the stream count down
-    if joint and not mopa and not shared_gpu and os.environ.get("MOPA_BENCH_HOST_INPUTS", "1") != "0":
+    if full and joint and not mopa and not shared_gpu and os.environ.get("MOPA_BENCH_HOST_INPUTS", "1") != "0":
         host_batches = []
         for bt in batches:
             host_batches.append(dict(locs=bt["locs"].cpu(), feats=bt["feats"].cpu(), label=bt["label"].cpu(), img=bt["img"].cpu(),
@@ -921,8 +996,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     # HIP-event brackets for the roofline figures on every EVENT_STRIDE-th timed step: on every step they cost 2.8 % (joint) /
-    # 4.4 % (3d) of `value` (MOPA_BENCH_EVENT_STRIDE=1 / =0 measure that: every step / never)
-    ev_stride = int(os.environ.get("MOPA_BENCH_EVENT_STRIDE", "5"))
+    # 4.4 % (3d) of `value` (MOPA_BENCH_EVENT_STRIDE=1 / =0 measure that: every step / never).  --full only: a plain run brackets nothing
+    ev_stride = int(os.environ.get("MOPA_BENCH_EVENT_STRIDE", "5")) if full else 0
+    capture = OutputCapture([("3d", model3d)] + ([("2d", model2d)] if joint else [])) if args.dump_outputs and rank == 0 else None
     n_ev_steps = 0
     t0 = time.perf_counter()
     per_step, step_times = [], os.environ.get("MOPA_BENCH_STEP_TIMES")
@@ -948,6 +1024,8 @@ def main():
         # the bracketed steps run in the SAME stream configuration as every other step (weight-gradient stream and 3D side stream
         # on): the brackets then time each launch as it runs inside `value`'s step, sharing the chip with the other streams --
         # which is also what `rocprofv3 --kernel-trace --stats` of this command reports (profiles/r3_final_*)
+        if capture is not None and i == args.steps - 1:
+            capture.arm()   # --dump-outputs: the forward outputs of the last timed step
         loss = paced_step(i)
         if step_times:   # diagnostics only (stderr): host clock after each step, "sync" adds a device sync per step
             if step_times == "sync":
@@ -981,9 +1059,22 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    loss_parts = loss if isinstance(loss, tuple) else (loss,)
     if isinstance(loss, tuple):   # decoupled streams: the four loss parts, read after the synchronisation above
         loss = sum(t.float() for t in loss)
     assert torch.isfinite(loss).item(), "loss is not finite"
+    if capture is not None:
+        # what the last timed step computed, before anything else runs: its loss parts, the networks' forward outputs, and the
+        # parameters after its Adam update with the gradients they were updated from (FlatAdam's flat buffers)
+        capture.disarm()
+        arrays = {"loss_parts": torch.stack([t.detach().float().reshape(()) for t in loss_parts])}
+        arrays.update(capture.outputs)
+        for tag, o in zip(("3d", "2d"), opts):
+            arrays[f"params{tag}"] = o.flat
+            arrays[f"grads{tag}"] = o.grad
+        nbytes = dump_outputs(args.dump_outputs, arrays)
+        print(f"[bench] --dump-outputs: {len(arrays)} arrays, {nbytes / 1e6:.1f} MB in {args.dump_outputs}", file=sys.stderr, flush=True)
+        capture = arrays = None
     host_value = None
     if host_batches is not None:   # same step, inputs handed over as host tensors (not part of `value`)
         n_host = max(2, min(args.steps, 8))
@@ -1025,7 +1116,7 @@ def main():
     # (train_xmuda_mopa.py:342-343,426-427).  `value` merges them (bn_groups / bn_group_points: an extension of the data_batch contract,
     # INTEGRATION.md); this is the same step without the extension, a few steps after the timed region, reported beside `value`.
     two_call_value = None
-    if joint and pair_mode and decoupled and os.environ.get("MOPA_BENCH_TWO_CALLS", "1") != "0":
+    if full and joint and pair_mode and decoupled and os.environ.get("MOPA_BENCH_TWO_CALLS", "1") != "0":
         n_two = max(2, min(args.steps, 8))
         mode["pair"] = False
         two_call_value = (timed_extra(n_two), n_two)
@@ -1036,7 +1127,7 @@ def main():
     # every sparse-conv launch sits in a HIP-event bracket on its stream.  Inside the timed step the family shares the chip and a
     # lower-priority stream with the 2D GEMMs: a bracket there is mostly queue wait (kept as frac_event_bracket_with_queue_wait).
     ks_alone = None
-    if joint and rank == 0 and pair_mode and pair2d[1] is not None and os.environ.get("MOPA_BENCH_SPARSE_ALONE", "1") != "0":
+    if full and joint and rank == 0 and pair_mode and pair2d[1] is not None and os.environ.get("MOPA_BENCH_SPARSE_ALONE", "1") != "0":
         p3 = pair2d[1]
         lab3 = torch.cat([batches[0]["label"], batches[1]["label"]])
         ks_main_records = timer.records
@@ -1091,7 +1182,7 @@ def main():
             return os.path.join(ROOT, "profiles", f"r6_{name}")
 
         fam_path = _prof("rocprof_family.json")
-        famj = json.load(open(fam_path)) if os.path.exists(fam_path) else {}
+        famj = json.load(open(fam_path)) if full and os.path.exists(fam_path) else {}
         # (every workload has its own PMC passes: the paired steps run both domains' scans as one sparse tensor -- other launches than
         #  `--workload 3d`'s)
         t3_key = wl_key
@@ -1146,7 +1237,7 @@ def main():
         roof = sp
         hbm_step = (None, None)
         tall = _prof(f"{wl_key}_hbm_traffic.json")
-        if os.path.exists(tall):
+        if full and os.path.exists(tall):
             tdat = json.load(open(tall))
             if tdat.get("_hbm_GB_per_step") is not None:
                 hbm_step = (tdat["_hbm_GB_per_step"], f"{os.path.relpath(tall, ROOT)} at commit {tdat.get('_commit', '?')} (rocprofv3 --pmc FETCH_SIZE / "
@@ -1155,7 +1246,7 @@ def main():
         traffic = None
         tpath = _prof(f"{wl_key}_hbm_traffic.json")  # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
         tj = {}
-        if joint and os.path.exists(tpath):                                      # of this same command (profiles/traffic.py)
+        if full and joint and os.path.exists(tpath):                                    # of this same command (profiles/traffic.py)
             tj = json.load(open(tpath))
             fam = [tj[k] for k in ("k_conv2d_igemm_mfma", "k_wino4_gemm_out", "k_wino4_conv", "k_wino4_conv32", "k_wino4_conv9") if k in tj]
             if fam:
@@ -1244,7 +1335,7 @@ def main():
                        "gradient_buckets_2d_bytes": bucket_bytes,
                        "winograd_f4_roles": ",".join(f4_roles()) if joint else None,
                        "winograd_f4_one_kernel_roles": (",".join(one_kernel_roles()) or None) if joint else None,
-                       "gradient_error_vs_fp64": gradient_error_vs_fp64() if joint else None,
+                       "gradient_error_vs_fp64": gradient_error_vs_fp64() if joint and full else None,
                        "scn_executor": "native (one C-ABI call per pass; bracketed steps walk the program from Python)" if native_default
                        else "python walk (MOPA_SCN_NATIVE=0)",
                        "net3d_pass": (None if not joint else "source + target scans as ONE sparse tensor (Net3DSeg bn_group_points: BatchNorm per domain "
@@ -1277,9 +1368,15 @@ def main():
             # command (profiles/make_final.sh -> traffic.py), never measured in this run -- the file and its commit say which build
             "hbm_GB_per_step": hbm_step[0], "hbm_GB_per_step_source": hbm_step[1],
             "peak_device_memory_GB": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2),   # caching-allocator high-water mark of this rank
+            "full": full,
         }
+        if not full:   # a plain run measured none of these: the line leaves them out
+            for k in ("value_with_host_inputs", "value_two_calls_per_domain", "two_calls_note", "host_inputs_note", "roofline",
+                      "roofline_wgrad", "roofline_sparse_conv", "hbm_GB_per_step", "hbm_GB_per_step_source"):
+                del line[k]
+            del line["config"]["gradient_error_vs_fp64"]
         print(f"[bench] timed {args.steps} steps in {elapsed:.3f}s (host enqueue {t_enqueued:.3f}s)", file=sys.stderr, flush=True)
-        if not args.no_cpu_baseline and world == 1:  # CPU baseline: rank 0 at N=1 only
+        if full and not args.no_cpu_baseline and world == 1:  # CPU baseline: rank 0 at N=1 only
             t_cpu = time.perf_counter()
             line["cpu_baseline"] = cpu_baseline_joint(model2d, model3d, shape=shape) if joint else cpu_baseline_3d(model3d)
             print(f"[bench] cpu baseline took {time.perf_counter() - t_cpu:.1f}s", file=sys.stderr, flush=True)

@@ -12,9 +12,9 @@ TITLE = {"3d": "Net3DSeg-only training step (bs 8, 1x MI355X) -- BASELINE config
          "joint": "joint 2D+3D xMUDA step (bs 8+8, 1x MI355X) -- BASELINE configs[2]",
          "kitti": "A2D2->SemanticKITTI-shape joint step (bs 2+2, 120,000-pt scans, 10 classes, 1x MI355X) -- BASELINE configs[4] per GPU",
          "mopa": "MoPA iteration (bs 4+4, VGI + third 3D pass + pseudo-label CE + SAM-mask loss, 1x MI355X) -- BASELINE configs[3] per GPU"}
-CMD = {"3d": "python bench.py --workload 3d --steps 50 --warmup 5", "joint": "python bench.py --steps 20 --warmup 5",
-       "kitti": "python bench.py --workload kitti --steps 10 --warmup 3",
-       "mopa": "python bench.py --workload mopa --steps 10 --warmup 3 --no-cpu-baseline"}
+CMD = {"3d": "python bench.py --workload 3d --steps 50 --warmup 5 --full", "joint": "python bench.py --steps 20 --warmup 5 --full",
+       "kitti": "python bench.py --workload kitti --steps 10 --warmup 3 --full",
+       "mopa": "python bench.py --workload mopa --steps 10 --warmup 3 --full --no-cpu-baseline"}
 STEPS = {"3d": 57, "joint": 37, "kitti": 25, "mopa": 15}   # steps traced by make_final.sh (setup + warm-up + timed + host-input steps)
 FAMILY = {"sparse_conv": ("k_spconv_t4", "k_spconv_pipe", "k_spconv_fwd", "k_spconv_blk", "k_spconv_run", "k_spconv_stem"),
           "dense_mfma": ("k_conv2d_igemm_mfma", "k_wino4_gemm_out", "k_wino4_conv", "k_wino4_conv32", "k_wino4_conv9"),
@@ -43,7 +43,7 @@ for w in ("3d", "joint", "kitti", "mopa"):
     stats = open(os.path.join(F, f"stats_{w}.md")).read()
     with open(os.path.join(R, f"{RND}_final_{w}_kernel_stats.md"), "w") as f:
         f.write(f"# Round {RND[1:]} final: {TITLE[w]}\n\nTaken at commit `{commit}`.  Commands (profiles/make_final.sh): `{CMD[w]}` (bench line) and "
-                f"`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py ... <same --steps / --warmup> --no-cpu-baseline` "
+                f"`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py ... <same --steps / --warmup> --full --no-cpu-baseline` "
                 f"(every step traced, warm-up included"
                 + ("; the 3D branch runs on a second stream, so kernel times overlap and their sum exceeds wall time" if w != "3d" else "")
                 + f").\n\n```\n{line}\n```\n\n{stats}")

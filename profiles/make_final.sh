@@ -4,11 +4,11 @@
 # Everything lands in gpurun_out/final/; copy the summaries into profiles/ afterwards (profiles/collect_final.py).
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/final; mkdir -p $O
-timeout 900 python3 bench.py --steps 20 --warmup 5 > $O/bench_joint.json 2> $O/bench_joint.err   # the driver's command
+timeout 900 python3 bench.py --steps 20 --warmup 5 --full > $O/bench_joint.json 2> $O/bench_joint.err   # the headline command, with every figure beside `value`
 # (after the joint run: the host-bound 3D-only step is the one that suffers from a cold box -- first process, page cache)
-timeout 600 python3 bench.py --workload 3d --steps 50 --warmup 5 > $O/bench_3d.json 2> $O/bench_3d.err
-timeout 600 python3 bench.py --workload mopa --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_mopa.json 2> $O/bench_mopa.err
-timeout 600 python3 bench.py --workload kitti --steps 10 --warmup 3 > $O/bench_kitti.json 2> $O/bench_kitti.err   # BASELINE configs[4] per GPU
+timeout 600 python3 bench.py --workload 3d --steps 50 --warmup 5 --full > $O/bench_3d.json 2> $O/bench_3d.err
+timeout 600 python3 bench.py --workload mopa --steps 10 --warmup 3 --full --no-cpu-baseline > $O/bench_mopa.json 2> $O/bench_mopa.err
+timeout 600 python3 bench.py --workload kitti --steps 10 --warmup 3 --full > $O/bench_kitti.json 2> $O/bench_kitti.err   # BASELINE configs[4] per GPU
 # The trace / counter passes run the SAME timed command; the two extra measurements bench.py makes after its timed region (the
 # reference's two-calls-per-domain loop order, the merged 3D pass alone with every sparse-conv launch bracketed) are switched off for
 # them: they launch the sparse-conv family on other batch sizes and would mix into the per-family averages.
@@ -17,9 +17,9 @@ for W in 3d joint kitti mopa; do
   A=""; [ $W = 3d ] && A="--workload 3d"; [ $W = kitti ] && A="--workload kitti"; [ $W = mopa ] && A="--workload mopa"
   # kernel statistics of the SAME command the bench line comes from (joint: --steps 20 --warmup 5 = the driver's; 25 steps traced)
   S="--steps 20 --warmup 5"; [ $W = 3d ] && S="--steps 50 --warmup 5"; [ $W = kitti ] && S="--steps 10 --warmup 3"; [ $W = mopa ] && S="--steps 10 --warmup 3"
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$W -o run -- python3 bench.py $A $S --no-cpu-baseline > $O/trace_$W.log 2>&1
-  timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$W -o run -- python3 bench.py $A --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_fetch_$W.log 2>&1
-  timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_$W -o run -- python3 bench.py $A --steps 2 --warmup 1 --no-cpu-baseline > $O/pmc_write_$W.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$W -o run -- python3 bench.py $A $S --full --no-cpu-baseline > $O/trace_$W.log 2>&1
+  timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_$W -o run -- python3 bench.py $A --steps 2 --warmup 1 --full --no-cpu-baseline > $O/pmc_fetch_$W.log 2>&1
+  timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_$W -o run -- python3 bench.py $A --steps 2 --warmup 1 --full --no-cpu-baseline > $O/pmc_write_$W.log 2>&1
   N=37; [ $W = 3d ] && N=57; [ $W = kitti ] && N=25; [ $W = mopa ] && N=15   # joint: 2 setup + 5 warm-up + 20 timed + 2 + 8 steps of the host-inputs measurement (kitti: 2 + 3 + 10 + 2 + 8)
   python3 profiles/summarize.py $O/trace_$W/run_kernel_stats.csv $N > $O/stats_$W.md
   NETS=2; [ $W = 3d ] && NETS=1

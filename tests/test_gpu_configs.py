@@ -443,7 +443,8 @@ def test_config4_joint_step_at_the_per_gpu_batch():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "kitti", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "kitti", "--steps", "3", "--warmup", "2", "--full",
+                        "--no-cpu-baseline"],
                        cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -453,3 +454,34 @@ def test_config4_joint_step_at_the_per_gpu_batch():
     assert c["points_per_scan"] == 120000 and c["num_classes"] == 10 and c["scans_per_step_per_gpu"] == 4 and d["value"] > 0
     assert d["roofline"]["bound"] == "mfma" and d["roofline_sparse_conv"]["algorithmic_bytes_per_launch"] > 0
     assert 0 < d["peak_device_memory_GB"] < 64        # 288 GB of HBM per GPU: the shape fits many times over
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the contract's keys, K timed steps, `ms_per_step` consistent
+    with `value`, none of the --full figures, and what the last timed step computed as float32 .npy files within 64 MB (loss parts,
+    both networks' forward outputs, parameters and gradients of both networks, all finite)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--dump-outputs", str(out)], cwd=root, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["full"] is False and d["unit"] == "scans/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32" and d["value"] > 0
+    assert abs(d["ms_per_step"] - 1e3 * d["config"]["scans_per_step_per_gpu"] / d["value"]) <= 0.01 * d["ms_per_step"]
+    for k in ("roofline", "roofline_wgrad", "roofline_sparse_conv", "cpu_baseline", "value_with_host_inputs", "value_two_calls_per_domain"):
+        assert k not in d, k
+    files = {f.name[:-4]: f for f in out.iterdir()}
+    assert all(f.suffix == ".npy" for f in out.iterdir())
+    assert {"loss_parts", "params2d", "grads2d", "params3d", "grads3d", "out2d_0_seg_logit", "out3d_0_seg_logit"} <= set(files), sorted(files)
+    assert sum(f.stat().st_size for f in files.values()) <= 64_000_000
+    for name, f in files.items():
+        a = np.load(f)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+    assert np.abs(np.load(files["grads2d"])).max() > 0 and np.abs(np.load(files["grads3d"])).max() > 0

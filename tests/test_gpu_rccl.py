@@ -36,7 +36,7 @@ def _launch(script_args, timeout):
 @pytest.mark.parametrize("buckets", [4, 0])
 def test_bench_joint_step_one_rank_over_rccl(buckets, monkeypatch):
     monkeypatch.setenv("MOPA_BENCH_BUCKETS", str(buckets))
-    r = _launch([os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--no-cpu-baseline"], 900)
+    r = _launch([os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--full", "--no-cpu-baseline"], 900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

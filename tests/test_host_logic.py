@@ -317,3 +317,27 @@ def test_weight_gradient_dispatcher_follows_the_measured_table():
         assert want(8, rows, cin, cout, 1) == pick, (rows, cin, cout)
     assert want(27, 49022, 20, 64, 0) == 0 and want(27, 49022, 64, 120, 0) == 0 and want(27, 49022, 272, 64, 0) == 0   # unsupported shapes
     assert query("mopa_spconv_wgrad_run_workspace_bytes", 27, 49022, 128, 64, 0) >= 27 * 128 * 64 * 4
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per array; small arrays whole, large ones as the same seeded, sorted sample of their
+    elements in every run (a parameter buffer and its gradient buffer of one size: the same elements), 64 MB at most in all."""
+    import bench
+    big = torch.arange(4_000_000, dtype=torch.float64)
+    arrays = {"loss_parts": torch.tensor([0.5, 1.5]), "small": torch.ones(3, 4, dtype=torch.float64)}
+    arrays.update({f"big{i}": big * (i + 1) for i in range(24)})
+    for run in ("a", "b"):
+        total = bench.dump_outputs(str(tmp_path / run), arrays)
+        assert total <= bench.DUMP_BUDGET_BYTES
+    got = {}
+    for run in ("a", "b"):
+        got[run] = {p.name: np.load(p) for p in (tmp_path / run).iterdir()}
+        assert set(got[run]) == {f"{n}.npy" for n in arrays}
+        assert all(a.dtype == np.float32 for a in got[run].values())
+    for name in got["a"]:
+        np.testing.assert_array_equal(got["a"][name], got["b"][name])
+    np.testing.assert_array_equal(got["a"]["loss_parts.npy"], [0.5, 1.5])
+    assert got["a"]["small.npy"].shape == (3, 4)
+    s0, s5 = got["a"]["big0.npy"], got["a"]["big5.npy"]
+    assert 0 < s0.size < 4_000_000 and s0.ndim == 1 and np.all(np.diff(s0) > 0)   # sampled, ascending, no repeats
+    np.testing.assert_array_equal(s5, 6 * s0)                                        # same element indices in every array of that size
