@@ -246,9 +246,11 @@ MOPA_API int mopa_bnrelu_rows_fwd(const float* x, int32_t ldx, float* y, int32_t
 // ------------------------------------------------------------------------------------------ BN backward
 // dz = dy * act'(.)  where the activation mask comes from the saved output y (ymask, needed when a residual was
 // added) or is recomputed from x (ymask == null).  act == 0: dz = dy.  Partial sums of dz and dz*xhat.
-__device__ __forceinline__ float bn_dz(float g, float xv, float sc, float sh, float leak, int act, const float* ym, int j) {
+// (The saved output arrives by value: a pointer into the caller's per-row register array, null when there is no ymask, made the
+// compiler keep that array in scratch -- 32 B per lane stored and re-loaded for every row in the partial and apply kernels.)
+__device__ __forceinline__ float bn_dz(float g, float xv, float sc, float sh, float leak, int act, bool has_ym, float ym) {
   if (!act) return g;
-  const float yv = ym ? ym[j] : fmaf(xv, sc, sh);
+  const float yv = has_ym ? ym : fmaf(xv, sc, sh);
   return yv > 0.f ? g : g * leak;
 }
 
@@ -291,7 +293,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
         const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w}, gs[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w}, ys[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask ? ys : nullptr, j);
+          const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
           s[j] += dz;
           ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
         }
@@ -305,7 +307,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
       const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask ? ys : nullptr, j);
+        const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
         s[j] += dz;
         ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
       }
@@ -374,7 +376,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
     float o[4], dzv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask ? ys : nullptr, j);
+      const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
       dzv[j] = dz;
       if (training) {
         const float xhat = (xs[j] - mean[j]) * inv[j];
