@@ -164,6 +164,10 @@ SIGNATURES = {
     "mopa_mask_cons_state_floats": ("z", "ii"),
     "mopa_mask_cons_fwd": ("i", "ppiiiiipppzp"),
     "mopa_mask_cons_bwd": ("i", "ppiiiiipppp"),
+    # ---- validation metrics (evaluate.hip)
+    "mopa_eval_logits_workspace_bytes": ("z", "ii"),
+    "mopa_eval_logits": ("i", "plplpiipiippppppppzp"),
+    "mopa_confusion_update": ("i", "pplpiipp"),
     # ---- optimiser (optim.hip)
     "mopa_adam_flat": ("i", "pppplffffffffp"),
 }

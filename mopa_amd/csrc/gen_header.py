@@ -56,6 +56,9 @@ SECTIONS = [
  * occupancy (mopa/data/mixmatch_ss.py:215-331 check_overlap), centre filters (:139-160), ground-cell lookup and road height
  * (:355-455 obj_on_road), range-image occlusion culling (mopa/data/utils/augmentation_3d.py:81-111,161-290) and the float64
  * voxeliser of post_process (mixmatch_ss.py:458-559)."""),
+    ("evaluate.hip", """Validation metrics on the device: predictions, confusion matrices, logged entropy means and CE losses, pseudo-label dump
+ * (mopa/data/utils/validate.py:112-170,184-185) and Evaluator.update (mopa/data/utils/evaluate.py:12-26: sklearn confusion_matrix
+ * with labels=) without host round trips.  Confusion matrices are int64 (n_labels, n_labels), rows = ground truth, added to."""),
     ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3)."""),
 ]
 
