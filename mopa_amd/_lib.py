@@ -168,6 +168,13 @@ SIGNATURES = {
     "mopa_eval_logits_workspace_bytes": ("z", "ii"),
     "mopa_eval_logits": ("i", "plplpiipiippppppppzp"),
     "mopa_confusion_update": ("i", "pplpiipp"),
+    # ---- 2D input pipeline (imageprep.hip)
+    "mopa_imageprep_resize_u8": ("i", "piiipipiiiipp"),
+    "mopa_imageprep_contrast_sums": ("i", "piliipppp"),
+    "mopa_imageprep_pixels": ("i", "piliippppppppp"),
+    "mopa_imageprep_mask_workspace_bytes": ("z", "i"),
+    "mopa_imageprep_mask": ("i", "piiippiiiipppiipppzp"),
+    "mopa_imageprep_indices": ("i", "ppiiiddpipppppp"),
     # ---- optimiser (optim.hip)
     "mopa_adam_flat": ("i", "pppplffffffffp"),
 }

@@ -59,6 +59,11 @@ SECTIONS = [
     ("evaluate.hip", """Validation metrics on the device: predictions, confusion matrices, logged entropy means and CE losses, pseudo-label dump
  * (mopa/data/utils/validate.py:112-170,184-185) and Evaluator.update (mopa/data/utils/evaluate.py:12-26: sklearn confusion_matrix
  * with labels=) without host round trips.  Confusion matrices are int64 (n_labels, n_labels), rows = ground truth, added to."""),
+    ("imageprep.hip", """The 2D half of the input pipeline on the device: Pillow's 8-bit BILINEAR resize, the three ImageEnhance blends behind
+ * torchvision's ColorJitter, flip + /255. + normalisation into the CHW batch tensor, scipy's order-0 zoom + refine_sam_mask, and
+ * the image-index transforms of Dataset.__getitem__ (mopa/data/nuscenes/nuscenes_dataloader.py:347-408,
+ * mopa/data/semantic_kitti/semantic_kitti_dataloader.py:563-630, mopa/data/utils/refine_pseudo_labels.py:72-102); bit-exact.
+ * Per-image pointers and draws are small host arrays (at most 32 images per call); one launch per stage for the whole batch."""),
     ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3)."""),
 ]
 
