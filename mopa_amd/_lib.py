@@ -175,6 +175,15 @@ SIGNATURES = {
     "mopa_imageprep_mask_workspace_bytes": ("z", "i"),
     "mopa_imageprep_mask": ("i", "piiippiiiipppiipppzp"),
     "mopa_imageprep_indices": ("i", "ppiiiddpipppppp"),
+    # ---- 3D input pipeline (scanprep.hip)
+    "mopa_scanprep_rotate": ("i", "ppppip"),
+    "mopa_scanprep_workspace_bytes": ("z", "l"),
+    "mopa_scanprep_rows_per_block": ("i", ""),
+    "mopa_scanprep_count": ("i", "pppppiifiipppzp"),
+    "mopa_scanprep_compact": ("i", "pppppiiifiipppplppppzp"),
+    "mopa_scanprep_take": ("i", "pllpipipllpppppppppp"),
+    "mopa_refine_pseudo_labels_segmented_workspace_bytes": ("z", "ii"),
+    "mopa_refine_pseudo_labels_segmented": ("i", "ppippiilpzp"),
     # ---- optimiser (optim.hip)
     "mopa_adam_flat": ("i", "pppplffffffffp"),
 }

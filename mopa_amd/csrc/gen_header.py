@@ -64,6 +64,13 @@ SECTIONS = [
  * the image-index transforms of Dataset.__getitem__ (mopa/data/nuscenes/nuscenes_dataloader.py:347-408,
  * mopa/data/semantic_kitti/semantic_kitti_dataloader.py:563-630, mopa/data/utils/refine_pseudo_labels.py:72-102); bit-exact.
  * Per-image pointers and draws are small host arrays (at most 32 images per call); one launch per stage for the whole batch."""),
+    ("scanprep.hip", """The 3D half of the input pipeline on the device, all scans of an iteration per launch: rotation, voxel coordinates
+ * and in-field filter of augment_and_scale_3d + Dataset.__getitem__ (mopa/data/utils/augmentation_3d.py:48-59,
+ * mopa/data/nuscenes/nuscenes_dataloader.py:339-340,410-465, mopa/data/semantic_kitti/semantic_kitti_dataloader.py:583-585,632-676),
+ * one ordered compaction of every per-point array into the layout of collate_scn_base (mopa/data/collate.py:182-264) and
+ * refine_pseudo_labels (mopa/data/utils/refine_pseudo_labels.py:5-22) for many (array, scan) segments at once; same bits as
+ * mopa_rotate_points_f32 + mopa_voxelize per scan.  Per-scan pointers, sizes and draws are small host arrays (at most 32 scans,
+ * 64 segments per call)."""),
     ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3)."""),
 ]
 
