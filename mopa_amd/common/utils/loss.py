@@ -18,10 +18,6 @@ import os as _os
 VALIDATE_LABELS = _os.environ.get("MOPA_VALIDATE_LABELS", "0") == "1"   # host-syncing range checks (see seg_ce)
 
 
-def _ws(n, dev):
-    return workspace.get(max(int(n), 256), dev)
-
-
 def _f32c(t):
     return t.contiguous().float()
 
@@ -32,7 +28,7 @@ class _SoftmaxKL(torch.autograd.Function):
         a, b = _f32c(logit_p), _f32c(logit_q.detach())
         N, C = a.shape
         loss = torch.empty((), dtype=torch.float32, device=a.device)
-        ws = _ws(query("mopa_loss_workspace_bytes", N), a.device)
+        ws = workspace.get(query("mopa_loss_workspace_bytes", N), a.device)
         call("mopa_softmax_kl_fwd", ptr(a), ptr(b), N, C, ptr(loss), ptr(ws), ws.numel(), stream())
         ctx.save_for_backward(a, b)
         return loss
@@ -61,7 +57,7 @@ class _WeightedCE(torch.autograd.Function):
         N, C = z.shape
         out = torch.empty(2, dtype=torch.float32, device=z.device)  # loss, normaliser
         status = torch.zeros(1, dtype=torch.int32, device=z.device)
-        ws = _ws(query("mopa_loss_workspace_bytes", N), z.device)
+        ws = workspace.get(query("mopa_loss_workspace_bytes", N), z.device)
         call("mopa_wce_fwd", ptr(z), ptr(y), ptr(w), N, C, ignore_index, ptr(out), ptr(out, 1), ptr(status), ptr(ws),
              ws.numel(), stream())
         ctx.save_for_backward(z, y, out)
@@ -130,7 +126,7 @@ class _MaskCons(torch.autograd.Function):
         k_norm = p.shape[1]  # quirk: the caller passes (B,H,W,C), so the normaliser is log2(H)
         loss = torch.empty((), dtype=torch.float32, device=p.device)
         state = torch.empty(query("mopa_mask_cons_state_floats", B, C), dtype=torch.float32, device=p.device)
-        ws = _ws(query("mopa_mask_cons_workspace_bytes", B, HW, C), p.device)
+        ws = workspace.get(query("mopa_mask_cons_workspace_bytes", B, HW, C), p.device)
         call("mopa_mask_cons_fwd", ptr(p), ptr(masks), B, HW, C, k_norm, int(min_entropy), ptr(loss), ptr(state),
              ptr(ws), ws.numel(), stream())
         ctx.save_for_backward(p, masks, state)

@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
-"""Regenerate include/mopa_hip.h from the MOPA_API definitions in csrc/*.hip (prototypes only; the section
-comments -- which reference interface each group replaces -- are maintained here)."""
+"""Everything that describes the C ABI, generated from the MOPA_API definitions in csrc/*.hip, which are parsed once (`parse`):
+
+  include/mopa_hip.h            the prototypes (the section comments -- which reference interface each group replaces -- are
+                                maintained here)
+  mopa_amd/csrc/exec_table.inc  the dispatch table of the command-list executor (exec2d.hip)
+  mopa_amd/_abi.py              the ctypes signatures of mopa_amd/_lib.py and the host-pointer parameters of every entry point
+
+`generate()` returns the three texts, `main()` writes them; tests/test_cabi.py asserts that the committed files are what it returns."""
+import collections
 import os
 import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.path.join(HERE, "..", "..", "include", "mopa_hip.h")
+ROOT = os.path.normpath(os.path.join(HERE, "..", ".."))
 
 SECTIONS = [
     ("hash3d.hip", """Voxel hash, active sets and rule tables (integer; bit-exact with oracle/scn3d.py::Geometry).
@@ -97,99 +104,105 @@ extern "C" {
 """
 
 
-def protos(path):
-    src = open(path).read()
+RETURNS = {"int": "i", "size_t": "z"}
+SCALARS = {"int": "i", "int32_t": "i", "int64_t": "l", "uint64_t": "u", "size_t": "z", "float": "f", "double": "d"}
+
+Param = collections.namedtuple("Param", "ctype name pointer code")          # code: 'p' for a pointer, else SCALARS[ctype]
+Proto = collections.namedtuple("Proto", "file name ret params text")       # text: the definition's head on one line
+
+
+def parse(fname):
+    """The MOPA_API definitions of one source file, in source order."""
     out = []
-    for m in re.finditer(r"MOPA_API\s+([^{;]+?)\s*\{", src, re.S):
-        sig = " ".join(m.group(1).split())
-        out.append(sig + ";")
+    for m in re.finditer(r"MOPA_API\s+([^{;]+?)\s*\{", open(os.path.join(HERE, fname)).read(), re.S):
+        text = " ".join(m.group(1).split())
+        ret, name, plist = re.match(r"(\w[\w\s\*]*?)\s*(mopa_\w+)\((.*)\)$", text).groups()
+        if ret not in RETURNS:
+            raise ValueError(f"{fname}: {name} returns `{ret}`; known return types: {', '.join(RETURNS)}")
+        params = []
+        for prm in re.sub(r"/\*.*?\*/", "", plist).split(","):
+            prm = prm.strip()
+            if prm in ("", "void"):
+                continue
+            pname = re.split(r"[\s\*]+", prm)[-1]
+            ctype = prm[:len(prm) - len(pname)].strip()
+            pointer = "*" in ctype
+            scalar = re.sub(r"\bconst\b", "", ctype).strip()
+            if not pointer and scalar not in SCALARS:
+                raise ValueError(f"{fname}: {name}: parameter `{prm}` has the scalar type `{scalar}`; known: {', '.join(SCALARS)}")
+            params.append(Param(ctype, pname, pointer, "p" if pointer else SCALARS[scalar]))
+        out.append(Proto(fname, name, ret, params, text))
     return out
 
 
-def gen_exec_table():
-    """csrc/exec_table.inc: one `case` per launching entry point (returns int, last parameter `void* stream`) for the command-list
-    executor of exec2d.hip -- arguments arrive as 64-bit slots (integers and pointers as int64, float / double as the bit pattern of
-    a double) and are cast back to the prototype's types.  Ids are positions in the sorted name list (mopa_exec_fn_id)."""
-    protos_all = []
-    for fname, _ in SECTIONS:
-        if fname == "exec2d.hip":
-            continue
-        protos_all += protos(os.path.join(HERE, fname))
-    fns = []
-    for sig in protos_all:
-        m = re.match(r"(\w[\w\s\*]*?)\s*(mopa_\w+)\((.*)\);$", sig)
-        ret, name, params = m.group(1).strip(), m.group(2), m.group(3)
-        if ret != "int" or not params.rstrip().endswith("void* stream"):
-            continue
-        types = []
-        for prm in params.split(","):
-            prm = re.sub(r"/\*.*?\*/", "", prm).strip()
-            t = prm[:prm.rindex(" ")].strip() if " " in prm else prm
-            if "*" in prm:
-                t = prm[:prm.rindex("*") + 1].strip()
-            types.append(t)
-        fns.append((name, types))
-    fns.sort()
+def gen_header(protos):
+    parts = [HEAD]
+    for fname, doc in SECTIONS:
+        parts.append(f"\n/* ---- {fname}\n * {doc}\n */")
+        parts += [p.text + ";" for p in protos if p.file == fname]
+    parts.append("\n#ifdef __cplusplus\n}\n#endif\n#endif /* MOPA_HIP_H */\n")
+    return "\n".join(parts)
+
+
+def gen_exec_table(protos):
+    """One `case` per launching entry point (returns int, last parameter `void* stream`) for the command-list executor of
+    exec2d.hip -- arguments arrive as 64-bit slots (integers and pointers as int64, float / double as the bit pattern of a double)
+    and are cast back to the prototype's types.  Ids are positions in the sorted name list (mopa_exec_fn_id)."""
+    fns = sorted((p.name, p.params) for p in protos if p.file != "exec2d.hip" and p.ret == "int" and p.params
+                 and (p.params[-1].ctype, p.params[-1].name) == ("void*", "stream"))
     lines = ["// GENERATED by gen_header.py::gen_exec_table from the MOPA_API prototypes; do not edit by hand.",
              "static const char* const EXEC_NAMES[] = {"]
     lines += [f'  "{n}",' for n, _ in fns]
     lines += ["};", f"static const int EXEC_N = {len(fns)};",
               "static int exec_dispatch(int id, const int64_t* a, int nargs) {", "  switch (id) {"]
-    for i, (n, types) in enumerate(fns):
+    for i, (n, params) in enumerate(fns):
         args = []
-        for j, t in enumerate(types):
-            if "*" in t:
-                args.append(f"({t})(uintptr_t)a[{j}]")
-            elif t in ("float", "double"):
-                args.append(f"({t})slot_f(a[{j}])")
+        for j, prm in enumerate(params):
+            if prm.pointer:
+                args.append(f"({prm.ctype})(uintptr_t)a[{j}]")
+            elif prm.code in "fd":
+                args.append(f"({prm.ctype})slot_f(a[{j}])")
             else:
-                args.append(f"({t})a[{j}]")
-        lines.append(f"    case {i}: return nargs == {len(types)} ? {n}({', '.join(args)}) : MOPA_ERR_ARG;")
+                args.append(f"({prm.ctype})a[{j}]")
+        lines.append(f"    case {i}: return nargs == {len(params)} ? {n}({', '.join(args)}) : MOPA_ERR_ARG;")
     lines += ["    default: return MOPA_ERR_ARG;", "  }", "}", ""]
-    with open(os.path.join(HERE, "exec_table.inc"), "w") as f:
-        f.write("\n".join(lines))
-    print("wrote exec_table.inc", len(fns), "entry points")
+    return "\n".join(lines)
 
 
-def gen_host_args():
-    """mopa_amd/_host_args.py: for every entry point, the positions and names of its HOST-pointer parameters (names ending in
-    `_host`).  The command-list recorder (mopa_amd/_lib.py::CommandList) copies those it knows the size of into its own blob and
-    refuses to record an entry point with any other one -- a recorded raw host address would dangle at replay."""
-    table = {}
+def gen_abi(protos):
+    """The ctypes table of mopa_amd/_lib.py, and for every entry point the positions and names of its HOST-pointer parameters
+    (names ending in `_host`).  The command-list recorder (mopa_amd/_lib.py::CommandList) copies those it knows the size of into
+    its own blob and refuses to record an entry point with any other one -- a recorded raw host address would dangle at replay."""
+    lines = ['"""GENERATED by csrc/gen_header.py from the MOPA_API definitions; do not edit by hand.',
+             "SIGNATURES: entry point -> (return code, argument codes): 'p' pointer, 'i' int / int32_t, 'l' int64_t, 'u' uint64_t,",
+             "'z' size_t, 'f' float, 'd' double.",
+             'HOST_PARAMS: entry point -> {argument position: name} of its host-pointer parameters (names ending in _host)."""',
+             "SIGNATURES = {"]
     for fname, _ in SECTIONS:
-        for sig in protos(os.path.join(HERE, fname)):
-            m = re.match(r"(\w[\w\s\*]*?)\s*(mopa_\w+)\((.*)\);$", sig)
-            name, params = m.group(2), m.group(3)
-            host = {}
-            for j, prm in enumerate(params.split(",")):
-                prm = re.sub(r"/\*.*?\*/", "", prm).strip()
-                pname = re.split(r"[\s\*]+", prm)[-1]
-                if pname.endswith("_host") and "*" in prm:
-                    host[j] = pname
-            if host:
-                table[name] = host
-    out = os.path.join(HERE, "..", "_host_args.py")
-    with open(out, "w") as f:
-        f.write('"""GENERATED by csrc/gen_header.py::gen_host_args from the MOPA_API prototypes; do not edit by hand.\n'
-                'entry point -> {argument position: name} of its host-pointer parameters (names ending in _host)."""\n')
-        f.write("HOST_PARAMS = {\n")
-        for n in sorted(table):
-            f.write(f"    {n!r}: {table[n]!r},\n")
-        f.write("}\n")
-    print("wrote _host_args.py", len(table), "entry points with host pointers")
+        lines.append(f"    # ---- {fname}")
+        lines += [f"    {p.name!r}: ({RETURNS[p.ret]!r}, {''.join(q.code for q in p.params)!r})," for p in protos if p.file == fname]
+    lines += ["}", "", "HOST_PARAMS = {"]
+    for p in sorted(protos, key=lambda p: p.name):
+        host = {j: q.name for j, q in enumerate(p.params) if q.pointer and q.name.endswith("_host")}
+        if host:
+            lines.append(f"    {p.name!r}: {host!r},")
+    lines += ["}", ""]
+    return "\n".join(lines)
+
+
+def generate():
+    """-> {path relative to the repository root: text} of every generated file."""
+    protos = [p for fname, _ in SECTIONS for p in parse(fname)]
+    return {"include/mopa_hip.h": gen_header(protos),
+            "mopa_amd/csrc/exec_table.inc": gen_exec_table(protos),
+            "mopa_amd/_abi.py": gen_abi(protos)}
 
 
 def main():
-    gen_exec_table()
-    gen_host_args()
-    parts = [HEAD]
-    for fname, doc in SECTIONS:
-        parts.append(f"\n/* ---- {fname}\n * {doc}\n */")
-        parts.extend(protos(os.path.join(HERE, fname)))
-    parts.append("\n#ifdef __cplusplus\n}\n#endif\n#endif /* MOPA_HIP_H */\n")
-    with open(OUT, "w") as f:
-        f.write("\n".join(parts))
-    print("wrote", os.path.normpath(OUT), sum(len(protos(os.path.join(HERE, f))) for f, _ in SECTIONS), "prototypes")
+    for path, text in generate().items():
+        with open(os.path.join(ROOT, path), "w") as f:
+            f.write(text)
+        print("wrote", path)
 
 
 if __name__ == "__main__":

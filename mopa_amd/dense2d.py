@@ -15,17 +15,13 @@ import numpy as np
 import torch
 
 from . import _lib, syncbn
-from ._lib import GradSink, call, ptr, query, stream, workspace
+from ._lib import GradSink, call, host_i32, ptr, query, stream, workspace
 from .sparse3d import View
 
 BN_EPS = 1e-5       # torch.nn.BatchNorm2d defaults
 BN_MOMENTUM = 0.1
 DEBUG = None  # tests may set this to a dict to capture intermediate gradients
 LAYERS = [("layer1", 64, 3, 1), ("layer2", 128, 4, 2), ("layer3", 256, 6, 2), ("layer4", 512, 3, 2)]
-
-
-def _ws(n, dev):
-    return workspace.get(max(int(n), 256), dev)
 
 
 class Img(View):
@@ -63,7 +59,7 @@ def _geom(**kw):
              "TH", "TW", "KH0", "KW0", "KS", "KWF", "Cin", "Cout", "ld_in", "ld_out"]
     d = dict(OS=1, OOY=0, OOX=0, IS=1, IY0=0, IX0=0, IDY=1, IDX=1, KH0=0, KW0=0, KS=1)
     d.update(kw)
-    return (ctypes.c_int32 * 25)(*[int(d[k]) for k in order])
+    return host_i32([d[k] for k in order])
 
 
 def igemm(x_ptr, w, bias, out_ptr, geom, accumulate=False):
@@ -79,7 +75,7 @@ def igemm_batched(x_ptr, w_ptr, out_ptr, geom, nbatch, in_stride, w_stride, out_
 def wgrad(x_ptr, dy_ptr, dw_ptr, geom, dev, accumulate=False, oihw=False):
     """oihw: dw_ptr is the parameter-layout gradient tensor itself (plain convolutions only), not the igemm layout."""
     wsb = query("mopa_conv2d_wgrad_workspace_bytes", ctypes.addressof(geom))
-    ws = _ws(wsb, dev)
+    ws = workspace.get(wsb, dev)
     call("mopa_conv2d_bwd_weight", x_ptr, dy_ptr, dw_ptr, ctypes.addressof(geom), int(accumulate) | (2 if oihw else 0), ptr(ws),
          ws.numel(), stream())
 
@@ -381,7 +377,7 @@ def wino_wgrad(x: Img, dout: Img, cin, cout, dw, V=None, accumulate=False, F=2, 
     B, H, W = x.B, x.H, x.W
     if F == 4 and V is None and (wino4_wgrad_fused(cin, cout, B, H, W) if fused is None else fused):
         bn = getattr(x, "bn", None)
-        ws = _ws(query("mopa_wino4_wgrad_fused_workspace_bytes", B, H, W, cin, cout), dev)
+        ws = workspace.get(query("mopa_wino4_wgrad_fused_workspace_bytes", B, H, W, cin, cout), dev)
         call("mopa_wino4_wgrad_fused", x.p, x.ld, ptr(bn[0]) if bn is not None else None, bn[1] if bn is not None else 1,
              bn[2] if bn is not None else 0, dout.p, dout.ld, B, H, W, cin, cout, ptr(dw), int(accumulate) | 2, ptr(ws), ws.numel(), stream())
         return
@@ -395,7 +391,7 @@ def wino_wgrad(x: Img, dout: Img, cin, cout, dw, V=None, accumulate=False, F=2, 
         else:
             call(f"mopa_wino{sfx}_input", x.p, x.ld, B, H, W, cin, ptr(V), stream())
     call(f"mopa_wino{sfx}_dout", dout.p, dout.ld, B, H, W, cout, ptr(dM), stream())
-    ws = _ws(query(f"mopa_wino{sfx}_wgrad_workspace_bytes", T, cin, cout), dev)
+    ws = workspace.get(query(f"mopa_wino{sfx}_wgrad_workspace_bytes", T, cin, cout), dev)
     call(f"mopa_wino{sfx}_bwd_weight", ptr(V), ptr(dM), T, cin, cout, ptr(dw), int(accumulate) | 2, ptr(ws), ws.numel(), stream())
 
 
@@ -618,7 +614,7 @@ class ConvTOp:
 
 def colsum(x: View, out: torch.Tensor, accumulate=False):
     wsb = query("mopa_colsum_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, out.device)
+    ws = workspace.get(wsb, out.device)
     call("mopa_colsum", x.p, x.ld, x.rows, x.C, ptr(out), int(accumulate), ptr(ws), ws.numel(), stream())
 
 
@@ -637,7 +633,7 @@ def bn_fwd(x: View, y: View, P, name, act, res, training, stats):
         return syncbn.fwd(x, y, P[name + ".weight"], P[name + ".bias"], P[name + ".running_mean"], P[name + ".running_var"],
                           BN_MOMENTUM, BN_EPS, 0.0, act, res, stats)
     wsb = query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     call("mopa_bn_act_fwd", x.p, x.ld, y.p, y.ld, x.rows, x.C, ptr(P[name + ".weight"]), ptr(P[name + ".bias"]),
          ptr(P[name + ".running_mean"]), ptr(P[name + ".running_var"]), BN_MOMENTUM, BN_EPS, 0.0, int(act),
          res.p if res is not None else None, res.ld if res is not None else 0, int(training), ptr(stats), ptr(ws),
@@ -650,7 +646,7 @@ def bn_fwd_groups(x: View, y: View | None, P, name, act, res, training, stats, G
     y = None: no apply pass (the consumer applies stats while it reads x: LazyImg)."""
     n = x.rows // G
     wsb = query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     call("mopa_bn_act_fwd_groups", x.p, x.ld, y.p if y is not None else None, y.ld if y is not None else 0, x.rows, x.C, G, n, 2 * n,
          ptr(P[name + ".weight"]), ptr(P[name + ".bias"]),
          ptr(P[name + ".running_mean"]), ptr(P[name + ".running_var"]), BN_MOMENTUM, BN_EPS, 0.0, int(act),
@@ -661,7 +657,7 @@ def bn_fwd_groups(x: View, y: View | None, P, name, act, res, training, stats, G
 def bn_bwd_groups(dy: View, x: View, dx: View, stats, act, ymask, dres, acc_dres, training, dgamma, dbeta, G, acc_params=False):
     n = x.rows // G
     wsb = query("mopa_bnrelu_rows_bwd_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     call("mopa_bn_act_bwd_groups", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act),
          ymask.p if ymask is not None else None, ymask.ld if ymask is not None else 0,
          dres.p if dres is not None else None, dres.ld if dres is not None else 0, int(acc_dres), int(training),
@@ -673,7 +669,7 @@ def bn_bwd(dy: View, x: View, dx: View, stats, act, ymask, dres, acc_dres, train
     if gathered is not None:   # the forward pass of this layer ran with global statistics
         return syncbn.bwd(dy, x, dx, stats, 0.0, act, ymask, dres, acc_dres, dgamma, dbeta, acc_params, acc_dx, gathered)
     wsb = query("mopa_bnrelu_rows_bwd_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     call("mopa_bn_act_bwd", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, ptr(stats), 0.0, int(act),
          ymask.p if ymask is not None else None, ymask.ld if ymask is not None else 0,
          dres.p if dres is not None else None, dres.ld if dres is not None else 0, int(acc_dres), int(training),
@@ -893,7 +889,7 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
                 # itself -- sums + parameter gradients here, no apply pass, no dx tensor
                 n = x.rows // G
                 coef = torch.empty(G, 2, x.C, dtype=torch.float32, device=dev)
-                ws = _ws(query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C), dev)
+                ws = workspace.get(query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C), dev)
                 call("mopa_bn_bwd_sums_groups", dy.p, dy.ld, x.p, x.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act), None, 0,
                      ptr(dg), ptr(db), int(pacc), ptr(coef), ptr(ws), ws.numel(), stream())
                 gmap[key(x)] = ("bn", dy, x, stats, coef)
@@ -957,7 +953,7 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
                 dwl = torch.empty(7, 2, 16, 64, dtype=torch.float32, device=dev)
                 if lazy:
                     _, bdy, bx, bstats, bcoef = lazy
-                    ws = _ws(query("mopa_conv2d_wgrad_workspace_bytes", ctypes.addressof(g)), dev)
+                    ws = workspace.get(query("mopa_conv2d_wgrad_workspace_bytes", ctypes.addressof(g)), dev)
                     call("mopa_stem_bwd_weight_bn", ptr(x4), bdy.p, bdy.ld, bx.p, bx.ld, ptr(bstats), ptr(bcoef), G, int(training), ptr(dwl),
                          ctypes.addressof(g), 0, ptr(ws), ws.numel(), stream())
                 else:
@@ -1259,10 +1255,10 @@ class Net2DFunction(torch.autograd.Function):
             rows = B * Hp * Wp
             row_start = torch.empty(rows + 1, dtype=torch.int32, device=dev)
             row_points = torch.empty(N, dtype=torch.int32, device=dev)
-            ws = _ws(query("mopa_points_csr_workspace_bytes", rows), dev)
+            ws = workspace.get(query("mopa_points_csr_workspace_bytes", rows), dev)
             call("mopa_points_csr", ptr(ctx.point_pix), N, rows, ptr(row_start), ptr(row_points), ptr(ws), ws.numel(),
                  stream())
-            ws = _ws(query("mopa_output_layer_heads_bwd_workspace_bytes", N, 64, C), dev)
+            ws = workspace.get(query("mopa_output_layer_heads_bwd_workspace_bytes", N, 64, C), dev)
             hnames = (["linear.weight", "linear.bias"] if dl1 is not None else []) + \
                      (["linear2.weight", "linear2.bias"] if dl2 is not None else [])
             hg, hacc = sink.take(*hnames)
@@ -1276,7 +1272,7 @@ class Net2DFunction(torch.autograd.Function):
             dfeat.t.zero_()
         if dpred is not None:
             (pw, pb), pacc = sink.take("linear.weight", "linear.bias")   # same tensors as the point head's, if it ran
-            ws = _ws(query("mopa_pixel_head_bwd_workspace_bytes", B, H, W, 64, C), dev)
+            ws = workspace.get(query("mopa_pixel_head_bwd_workspace_bytes", B, H, W, 64, C), dev)
             call("mopa_pixel_head_bwd", ptr(dpred), feat.p, feat.ld, B, Hp, Wp, H, W, 64, C, ptr(P["linear.weight"]),
                  dfeat.p, dfeat.ld, 1, ptr(pw), ptr(pb), int(head_w_acc or pacc), ptr(ws), ws.numel(), stream())
         dimg = None

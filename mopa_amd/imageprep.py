@@ -30,7 +30,7 @@ import math
 import numpy as np
 import torch
 
-from ._lib import call, ptr, query, stream, workspace
+from ._lib import call, chunk_ranges, host_addr, host_i32, host_ptrs, ptr, query, stream, workspace
 
 MAXB = 32                       # csrc/imageprep.hip IP_MAXB: images per launch
 PRECISION_BITS = 22             # Pillow: 32 - 8 - 2
@@ -166,14 +166,6 @@ def _on_gpu(items, what="images"):
     return [t.contiguous() for t in items]
 
 
-def _ptr_table(ptrs):
-    return (ctypes.c_void_p * len(ptrs))(*[p or None for p in ptrs])
-
-
-def _i32(values):
-    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
-
-
 def _jitter_tables(jitter, B):
     """list of (order, factors) or None per image -> (int32[B][3], float[B][3]) host arrays; (None, None) when nothing is on."""
     if jitter is None or all(j is None or len(j[0]) == 0 for j in jitter):
@@ -191,7 +183,7 @@ def _jitter_tables(jitter, B):
             if not (f >= 0):
                 raise ValueError(f"imageprep: jitter factor {f!r} of image {b} is negative")
             order[3 * b + k], factor[3 * b + k] = int(o), float(np.float32(f))
-    return _i32(order), (ctypes.c_float * (3 * B))(*factor)
+    return host_i32(order), (ctypes.c_float * (3 * B))(*factor)
 
 
 def _flags(flip, B):
@@ -200,7 +192,7 @@ def _flags(flip, B):
     flip = [flip] * B if isinstance(flip, (bool, np.bool_)) else list(flip)
     if len(flip) != B:
         raise ValueError(f"imageprep: {len(flip)} flip flags for {B} images")
-    return _i32([1 if f else 0 for f in flip])
+    return host_i32([1 if f else 0 for f in flip])
 
 
 def _windows(windows, B, H, W):
@@ -216,14 +208,6 @@ def _windows(windows, B, H, W):
             raise ValueError(f"imageprep: crop window {(l, t, r, b)} must lie inside the {W}x{H} image and all windows of a call "
                              f"must have one size")
     return windows, oh, ow
-
-
-def _addr(a):
-    return None if a is None else ctypes.addressof(a)
-
-
-def _chunks(B):
-    return [(s, min(s + MAXB, B)) for s in range(0, B, MAXB)]
 
 
 # ------------------------------------------------------------------------------------------------ 1. resize
@@ -243,9 +227,9 @@ def resize_bilinear_u8(images, size, out=None) -> torch.Tensor:
         out = torch.empty(B, h, w, 3, dtype=torch.uint8, device=dev)
     elif tuple(out.shape) != (B, h, w, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"resize_bilinear_u8: out must be a contiguous uint8 {(B, h, w, 3)} tensor on {dev}")
-    for s, e in _chunks(B):
-        tab = _ptr_table([t.data_ptr() for t in imgs[s:e]])
-        call("mopa_imageprep_resize_u8", _addr(tab), e - s, H, W, ptr(xtab), xt_host.shape[1] - 2, ptr(ytab), yt_host.shape[1] - 2,
+    for s, e in chunk_ranges(B, MAXB):
+        tab = host_ptrs(imgs[s:e])
+        call("mopa_imageprep_resize_u8", host_addr(tab), e - s, H, W, ptr(xtab), xt_host.shape[1] - 2, ptr(ytab), yt_host.shape[1] - 2,
              h, w, span, ptr(out[s:e]), stream())
     return out
 
@@ -268,15 +252,15 @@ def _pixels(imgs, windows, jitter, flip, dst_u8, dst_f32, normalizer, ori):
     base = [t.data_ptr() + ((windows[b][1] * W + windows[b][0]) * 3 if windows else 0) for b, t in enumerate(imgs)]
     has_contrast = order is not None and any(order[k] == CONTRAST for k in range(3 * B))
     sums = torch.empty(B, dtype=torch.int64, device=dev) if has_contrast else None
-    for s, e in _chunks(B):
-        tab = _ptr_table(base[s:e])
+    for s, e in chunk_ranges(B, MAXB):
+        tab = host_ptrs(base[s:e])
         o = None if order is None else ctypes.addressof(order) + 12 * s
         f = None if factor is None else ctypes.addressof(factor) + 12 * s
         fl = None if flags is None else ctypes.addressof(flags) + 4 * s
         if has_contrast:
-            call("mopa_imageprep_contrast_sums", _addr(tab), e - s, pitch, oh, ow, o, f, ptr(sums[s:e]), stream())
-        call("mopa_imageprep_pixels", _addr(tab), e - s, pitch, oh, ow, o, f, None if sums is None else ptr(sums[s:e]), fl,
-             None if dst_u8 is None else ptr(dst_u8[s:e]), None if dst_f32 is None else ptr(dst_f32[s:e]), _addr(norm),
+            call("mopa_imageprep_contrast_sums", host_addr(tab), e - s, pitch, oh, ow, o, f, ptr(sums[s:e]), stream())
+        call("mopa_imageprep_pixels", host_addr(tab), e - s, pitch, oh, ow, o, f, None if sums is None else ptr(sums[s:e]), fl,
+             None if dst_u8 is None else ptr(dst_u8[s:e]), None if dst_f32 is None else ptr(dst_f32[s:e]), host_addr(norm),
              None if ori is None else ptr(ori[s:e]), stream())
     return oh, ow
 
@@ -366,14 +350,14 @@ def prepare_sam_mask(masks, size=None, max_h=None, row_min=None, max_area_thre=0
     elif tuple(out.shape) != (B, oh, ow) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"prepare_sam_mask: out must be a contiguous int32 {(B, oh, ow)} tensor on {dev}")
     min_count = area_min_count(max_area_thre, h, w)
-    for s, e in _chunks(B):
-        tab = _ptr_table([t.data_ptr() for t in ms[s:e]])
-        lim = _i32(limits[s:e]) if mode == 1 else None
-        crop = _i32([v for wd in windows[s:e] for v in (wd[1], wd[0])]) if windows else None
+    for s, e in chunk_ranges(B, MAXB):
+        tab = host_ptrs(ms[s:e])
+        lim = host_i32(limits[s:e]) if mode == 1 else None
+        crop = host_i32([v for wd in windows[s:e] for v in (wd[1], wd[0])]) if windows else None
         fl = None if flags is None else ctypes.addressof(flags) + 4 * s
         ws = workspace.get(query("mopa_imageprep_mask_workspace_bytes", e - s), dev)
-        call("mopa_imageprep_mask", _addr(tab), e - s, H, W, ptr(ytab), ptr(xtab), h, w, min_count, mode, _addr(lim),
-             ptr(row_min[s:e]) if mode == 2 else None, _addr(crop), oh, ow, fl, ptr(out[s:e]), ptr(ws), ws.numel(), stream())
+        call("mopa_imageprep_mask", host_addr(tab), e - s, H, W, ptr(ytab), ptr(xtab), h, w, min_count, mode, host_addr(lim),
+             ptr(row_min[s:e]) if mode == 2 else None, host_addr(crop), oh, ow, fl, ptr(out[s:e]), ptr(ws), ws.numel(), stream())
     return out
 
 
@@ -433,12 +417,12 @@ def prepare_img_indices(points, src_size=None, size=None, windows=None, flip=Non
     ori_t = [torch.empty(n, 2, dtype=torch.int64, device=dev) for n in ns] if ori else None
     keep = [torch.empty(n, dtype=torch.uint8, device=dev) for n in ns] if windows is not None else None
     rmin = torch.empty(B, dtype=torch.int32, device=dev) if row_min else None
-    for s, e in _chunks(B):
-        tabs = [_ptr_table([t.data_ptr() for t in ts[s:e]]) if ts is not None else None for ts in (pts, idx, ori_t, keep)]
-        n_host, w_host = _i32(ns[s:e]), _i32([v for wd in win[s:e] for v in wd])
+    for s, e in chunk_ranges(B, MAXB):
+        tabs = [host_ptrs(ts[s:e]) if ts is not None else None for ts in (pts, idx, ori_t, keep)]
+        n_host, w_host = host_i32(ns[s:e]), host_i32([v for wd in win[s:e] for v in wd])
         fl = None if flags is None else ctypes.addressof(flags) + 4 * s
-        call("mopa_imageprep_indices", _addr(tabs[0]), _addr(n_host), e - s, 0 if pts[0].dtype == torch.float32 else 1, mode, sy, sx,
-             _addr(w_host), 0 if size is None else int(size[0]), fl, _addr(tabs[1]), _addr(tabs[2]), _addr(tabs[3]),
+        call("mopa_imageprep_indices", host_addr(tabs[0]), host_addr(n_host), e - s, 0 if pts[0].dtype == torch.float32 else 1, mode, sy, sx,
+             host_addr(w_host), 0 if size is None else int(size[0]), fl, host_addr(tabs[1]), host_addr(tabs[2]), host_addr(tabs[3]),
              None if rmin is None else ptr(rmin[s:e]), stream())
     res = {"img_indices": idx}
     if keep is not None:

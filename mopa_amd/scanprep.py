@@ -26,7 +26,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import call, ptr, query, stream, workspace
+from ._lib import call, chunk_ranges, host_addr, host_i32, host_ptrs, ptr, query, stream, workspace
 from .voxelize import draw_rotation
 
 MAXB = 32                       # csrc/scanprep.hip SP_MAXB: scans per launch
@@ -112,22 +112,6 @@ def _check_samples(samples, label_mapping):
             raise ValueError("prepare_batch_3d: all tensors of a call must be on one device")
 
 
-def _ptrs(ts):
-    return (ctypes.c_void_p * len(ts))(*[(t.data_ptr() if isinstance(t, torch.Tensor) else t) or None for t in ts])
-
-
-def _i32(values):
-    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
-
-
-def _addr(a):
-    return None if a is None else ctypes.addressof(a)
-
-
-def _chunks(B):
-    return [(s, min(s + MAXB, B)) for s in range(0, B, MAXB)]
-
-
 def _upload_i64(values, dev):
     """A few host integers -> device, asynchronously (no host synchronisation that torch would have to make)."""
     return torch.tensor(values, dtype=torch.int64).to(dev, non_blocking=True)
@@ -159,8 +143,7 @@ def refine_pseudo_labels_segmented(probs, pseudo_labels, ignore_label: int = -10
     if out is None:
         out = torch.empty(sum(ns), dtype=torch.int64, device=dev)
     outs = list(out.split(ns))
-    for s in range(0, len(labels), 2 * MAXB):
-        e = min(s + 2 * MAXB, len(labels))
+    for s, e in chunk_ranges(len(labels), 2 * MAXB):
         _refine_into(None if ps is None else ps[s:e], labels[s:e], outs[s:e], ignore_label, num_classes, dev)
     return outs
 
@@ -218,7 +201,7 @@ def prepare_batch_3d(samples, scale, full_scale: int = 4096, label_mapping=None,
             ps_flat[k] = torch.empty(total, dtype=torch.int64, device=dev)
         groups = [ps_keys] if len({side[k][0].dtype for k in ps_keys}) == 1 else [[k] for k in ps_keys]
         for g in groups:
-            for s, e in _chunks(B):
+            for s, e in chunk_ranges(B, MAXB):
                 labs = [t for k in g for t in side[k][s:e]]
                 prs = [t for k in g for t in side["probs" + k[-3:]][s:e]] if refine else None
                 views = [v for k in g for v in ps_flat[k][row0[s]:row0[e]].split(ns[s:e])]
@@ -231,32 +214,32 @@ def prepare_batch_3d(samples, scale, full_scale: int = 4096, label_mapping=None,
         buf = torch.empty(sum(ns[b] for b in rot_ids), 3, dtype=torch.float32, device=dev)
         for b, v in zip(rot_ids, buf.split([ns[b] for b in rot_ids])):
             src[b] = v
-        for s, e in _chunks(len(rot_ids)):
+        for s, e in chunk_ranges(len(rot_ids), MAXB):
             ids = rot_ids[s:e]
             r = np.ascontiguousarray(np.stack([np.asarray(samples[b]["rot"], np.float32) for b in ids]))
-            st, dt, nt = _ptrs([pts[b] for b in ids]), _ptrs([src[b] for b in ids]), _i32([ns[b] for b in ids])
-            call("mopa_scanprep_rotate", _addr(st), _addr(dt), _addr(nt), r.ctypes.data, len(ids), stream())
+            st, dt, nt = host_ptrs([pts[b] for b in ids]), host_ptrs([src[b] for b in ids]), host_i32([ns[b] for b in ids])
+            call("mopa_scanprep_rotate", host_addr(st), host_addr(dt), host_addr(nt), r.ctypes.data, len(ids), stream())
 
     # 2 + 3. min / max, keep flags, ordered counts -> offsets
     rows = query("mopa_scanprep_rows_per_block")
     n_outside = torch.zeros((), dtype=torch.int32, device=dev)
     chunks = []
-    for s, e in _chunks(B):
+    for s, e in chunk_ranges(B, MAXB):
         Bc = e - s
         seg_src = src[s:e] + (pts[s:e] if ema_input else [])
         seg_n = ns[s:e] * (2 if ema_input else 1)
         seg_keep = (side["keep_in"][s:e] + [None] * (Bc if ema_input else 0)) if has["keep_in"] else None
         S = len(seg_src)
         u = [float(v) for b in range(s, e) for v in (samples[b]["transl_u"] if samples[b].get("transl_u") is not None else (0., 0., 0.))]
-        c = {"S": S, "B": Bc, "s": s, "e": e, "src": _ptrs(seg_src), "keep": _ptrs(seg_keep) if seg_keep else None, "n": _i32(seg_n),
-             "u": (ctypes.c_double * (3 * Bc))(*u), "on": _i32([samples[b].get("transl_u") is not None for b in range(s, e)]),
-             "hold": (seg_src, seg_keep)}
+        c = {"S": S, "B": Bc, "s": s, "e": e, "src": host_ptrs(seg_src), "keep": host_ptrs(seg_keep) if seg_keep else None,
+             "n": host_i32(seg_n), "u": (ctypes.c_double * (3 * Bc))(*u),
+             "on": host_i32([samples[b].get("transl_u") is not None for b in range(s, e)]), "hold": (seg_src, seg_keep)}
         nblk = sum(-(-n // rows) for n in seg_n)
         c["ws"] = torch.empty(query("mopa_scanprep_workspace_bytes", nblk), dtype=torch.uint8, device=dev)
         c["flags"] = torch.empty(sum(seg_n), dtype=torch.uint8, device=dev) if general else None
         c["offsets"] = torch.empty(S + 1 + Bc + 1, dtype=torch.int64, device=dev) if general else None
-        call("mopa_scanprep_count", _addr(c["src"]), _addr(c["keep"]), _addr(c["n"]), _addr(c["u"]), _addr(c["on"]), S, Bc, scale, full_scale,
-             int(general), ptr(c["flags"]), ptr(c["offsets"]), ptr(c["ws"]), c["ws"].numel(), stream())
+        call("mopa_scanprep_count", host_addr(c["src"]), host_addr(c["keep"]), host_addr(c["n"]), host_addr(c["u"]), host_addr(c["on"]),
+             S, Bc, scale, full_scale, int(general), ptr(c["flags"]), ptr(c["offsets"]), ptr(c["ws"]), c["ws"].numel(), stream())
         chunks.append(c)
 
     # the one read-back: per chunk [first output row of every segment ..., first keep_in row of every scan ...]
@@ -292,9 +275,9 @@ def prepare_batch_3d(samples, scale, full_scale: int = 4096, label_mapping=None,
     m0 = k0 = o0 = 0
     for c in chunks:
         s, e, Bc = c["s"], c["e"], c["B"]
-        call("mopa_scanprep_compact", _addr(c["src"]), _addr(c["keep"]), _addr(c["n"]), _addr(c["u"]), _addr(c["on"]), c["S"], Bc, s, scale,
-             full_scale, int(not general), ptr(c["flags"]), locs_p + 32 * m0, None if ori_p is None else ori_p + 32 * o0,
-             gather_p + 8 * m0, int(row0[s]), None if mask1_p is None else mask1_p + k0,
+        call("mopa_scanprep_compact", host_addr(c["src"]), host_addr(c["keep"]), host_addr(c["n"]), host_addr(c["u"]), host_addr(c["on"]),
+             c["S"], Bc, s, scale, full_scale, int(not general), ptr(c["flags"]), locs_p + 32 * m0,
+             None if ori_p is None else ori_p + 32 * o0, gather_p + 8 * m0, int(row0[s]), None if mask1_p is None else mask1_p + k0,
              None if gather1_p is None else gather1_p + 8 * k0, ptr(n_outside), ptr(c["ws"]), c["ws"].numel(), stream())
         c["m0"], c["k0"] = m0, k0
         m0 += int(c["off"][Bc])
@@ -313,31 +296,31 @@ def prepare_batch_3d(samples, scale, full_scale: int = 4096, label_mapping=None,
     ps_out = {k: torch.empty(M, dtype=torch.int64, device=dev) for k in ps_keys} if not through else {}
     for c in chunks:
         s, e, Bc = c["s"], c["e"], c["B"]
-        nt = _i32(ns[s:e])
-        lt = _ptrs(side["seg_label"][s:e]) if has["seg_label"] else None
-        it = _ptrs(side["img_indices"][s:e]) if has["img_indices"] else None
-        st = _ptrs(src[s:e])
+        nt = host_i32(ns[s:e])
+        lt = host_ptrs(side["seg_label"][s:e]) if has["seg_label"] else None
+        it = host_ptrs(side["img_indices"][s:e]) if has["img_indices"] else None
+        st = host_ptrs(src[s:e])
         Mc, Kc, m0, k0, r0 = int(c["off"][Bc]), int(c["koff"][Bc]), c["m0"], c["k0"], int(row0[s])
         ps2, ps3 = ps_flat.get("pseudo_label_2d"), ps_flat.get("pseudo_label_3d")
         if through:
             if has["seg_label"]:
-                call("mopa_scanprep_take", None, 0, Mc, _addr(nt), Bc, _addr(lt), lab_dt, ptr(label_mapping),
+                call("mopa_scanprep_take", None, 0, Mc, host_addr(nt), Bc, host_addr(lt), lab_dt, ptr(label_mapping),
                      0 if label_mapping is None else label_mapping.numel(), int(ignore_label), None, None, None, None,
                      seg_out.data_ptr() + 8 * m0, None, None, None, None, stream())
             continue
-        call("mopa_scanprep_take", gather_p + 8 * m0, r0, Mc, _addr(nt), Bc, _addr(lt), lab_dt, ptr(label_mapping),
-             0 if label_mapping is None else label_mapping.numel(), int(ignore_label), _addr(it), _addr(st),
+        call("mopa_scanprep_take", gather_p + 8 * m0, r0, Mc, host_addr(nt), Bc, host_addr(lt), lab_dt, ptr(label_mapping),
+             0 if label_mapping is None else label_mapping.numel(), int(ignore_label), host_addr(it), host_addr(st),
              None if ps2 is None else ps2.data_ptr() + 8 * r0, None if ps3 is None else ps3.data_ptr() + 8 * r0,
              None if seg_out is None else seg_out.data_ptr() + 8 * m0, None if img_out is None else img_out.data_ptr() + 16 * m0,
              pts_out.data_ptr() + 12 * m0, None if ps2 is None else ps_out["pseudo_label_2d"].data_ptr() + 8 * m0,
              None if ps3 is None else ps_out["pseudo_label_3d"].data_ptr() + 8 * m0, stream())
         if orig_out is not None:                            # the mapped labels before the field filter (after keep_in)
             if has["keep_in"]:
-                call("mopa_scanprep_take", gather1_p + 8 * k0, r0, Kc, _addr(nt), Bc, _addr(lt), lab_dt, ptr(label_mapping),
+                call("mopa_scanprep_take", gather1_p + 8 * k0, r0, Kc, host_addr(nt), Bc, host_addr(lt), lab_dt, ptr(label_mapping),
                      0 if label_mapping is None else label_mapping.numel(), int(ignore_label), None, None, None, None,
                      orig_out.data_ptr() + 8 * k0, None, None, None, None, stream())
             else:
-                call("mopa_scanprep_take", None, 0, int(row0[e] - r0), _addr(nt), Bc, _addr(lt), lab_dt, ptr(label_mapping),
+                call("mopa_scanprep_take", None, 0, int(row0[e] - r0), host_addr(nt), Bc, host_addr(lt), lab_dt, ptr(label_mapping),
                      0 if label_mapping is None else label_mapping.numel(), int(ignore_label), None, None, None, None,
                      orig_out.data_ptr() + 8 * r0, None, None, None, None, stream())
 
@@ -376,6 +359,7 @@ def _refine_into(probs, labels, views, ignore_label, num_classes, dev):
     c = 32 if num_classes is None else int(num_classes)
     S = len(labels)
     ws = workspace.get(query("mopa_refine_pseudo_labels_segmented_workspace_bytes", S, c), dev)
-    pt, lt, ot, nt = (_ptrs(probs) if probs is not None else None), _ptrs(labels), _ptrs(views), _i32([t.numel() for t in labels])
-    call("mopa_refine_pseudo_labels_segmented", _addr(pt), _addr(lt), _LABEL_DTYPES[labels[0].dtype], _addr(nt), _addr(ot), S, c,
-         int(ignore_label), ptr(ws), ws.numel(), stream())
+    pt, lt, ot = (host_ptrs(probs) if probs is not None else None), host_ptrs(labels), host_ptrs(views)
+    nt = host_i32([t.numel() for t in labels])
+    call("mopa_refine_pseudo_labels_segmented", host_addr(pt), host_addr(lt), _LABEL_DTYPES[labels[0].dtype], host_addr(nt), host_addr(ot),
+         S, c, int(ignore_label), ptr(ws), ws.numel(), stream())

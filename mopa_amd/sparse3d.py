@@ -29,10 +29,6 @@ RUN_PATH = os.environ.get("MOPA_SPCONV_RUN", "1") != "0"             # the offse
 RUN_MAX_ROWS = 220000   # 27-offset tables above this get no run-major rulebook
 
 
-def _ws(nbytes, device):
-    return workspace.get(max(int(nbytes), 256), device)
-
-
 def _pow2_at_least(n):
     p = 1
     while p < n:
@@ -84,7 +80,7 @@ class Geometry3D:
             raise ValueError(f"group_points={group_points}: need at most two increasing point counts inside (0, {N})")
         meta = torch.zeros((1 + len(bounds)) * L + 1, **i32)   # counts[0..L-1], status, then per boundary: rows in front of it [0..L-1]
         wsb = query("mopa_voxel_hash_workspace_bytes", N)
-        ws = _ws(wsb, device)
+        ws = workspace.get(wsb, device)
         st = stream()
         call("mopa_voxel_hash_build", ptr(coords), N, ptr(tk[0]), ptr(tv[0]), cap, ptr(item_row[0]), ptr(keys[0]),
              ptr(meta), ptr(meta, L), ptr(ws), ws.numel(), st)
@@ -141,7 +137,7 @@ class Geometry3D:
         tg = torch.empty(ntile, **i32)
         gs = torch.empty(ntile + 1, **i32)
         call("mopa_rulebook_groups_count_batched", desc_h.data_ptr(), len(tables), ntile, ptr(tg), st)
-        ws = _ws(query("mopa_scan_workspace_bytes", ntile), device)
+        ws = workspace.get(query("mopa_scan_workspace_bytes", ntile), device)
         call("mopa_scan_exclusive_i32", ptr(tg), ptr(gs), ntile, ptr(gs, ntile), ptr(ws), ws.numel(), st)
         ng = max(sum(t.shape[0] * ((t.shape[1] + 15) // 16 + (t.shape[1] + 63) // 64) for t in tables), 1)
         go = torch.empty(ng, **i32)
@@ -168,7 +164,7 @@ class Geometry3D:
         self.row_start = torch.empty(A[0] + 1, **i32)
         self.row_points = torch.empty(N, **i32)
         wsb = query("mopa_points_csr_workspace_bytes", A[0])
-        ws = _ws(wsb, device)
+        ws = workspace.get(wsb, device)
         call("mopa_points_csr", ptr(self.point_row), N, A[0], ptr(self.row_start), ptr(self.row_points), ptr(ws),
              ws.numel(), st)
 
@@ -382,7 +378,7 @@ def spconv_launch(nbr: torch.Tensor, x: View, wk: torch.Tensor, out: View, w_fli
              int(w_flip) | 2, out.p, out.ld, 0, 0, stream())
     elif rb is not None and cin > 4 and (A_out + 63) // 64 < (1500 if K == 27 else 200):   # (<= 4 input channels: the stem kernel inside mopa_spconv_fwd)
         gs, go, gi, gout = rb
-        ws = _ws(query("mopa_spconv_grouped_workspace_bytes", K, A_out, cout), wk.device)
+        ws = workspace.get(query("mopa_spconv_grouped_workspace_bytes", K, A_out, cout), wk.device)
         call("mopa_spconv_fwd_grouped", ptr(gs), ptr(go), ptr(gi), ptr(gout), K, A_out, x.p, x.ld, cin, ptr(wk), cout,
              int(w_flip), out.p, out.ld, ptr(ws), ws.numel(), stream())
     else:
@@ -392,7 +388,7 @@ def spconv_launch(nbr: torch.Tensor, x: View, wk: torch.Tensor, out: View, w_fli
 def spconv_launch_run(runs, K: int, x: View, wk: torch.Tensor, out: View, w_flip: bool):
     """The offset-major convolution launch (gather-GEMM + ordered reduce) on a weight in the run layout (bench.py times this)."""
     buf, one = runs
-    ws = None if one else _ws(query("mopa_spconv_run_workspace_bytes", K, out.rows, out.C), wk.device)
+    ws = None if one else workspace.get(query("mopa_spconv_run_workspace_bytes", K, out.rows, out.C), wk.device)
     call("mopa_spconv_fwd_run", ptr(buf), K, out.rows, x.p, x.ld, x.C, ptr(wk), out.C, int(w_flip), out.p, out.ld, one,
          ptr(ws), 0 if ws is None else ws.numel(), stream())
 
@@ -408,7 +404,7 @@ def spconv_bwd_weight(nbr: torch.Tensor, x: View, dout: View, dw: torch.Tensor, 
     K, A_out = nbr.shape
     assert dw.shape == (K, x.C, dout.C) and dout.rows == A_out
     wsb = query("mopa_spconv_wgrad_workspace_bytes", K, A_out, x.C, dout.C)
-    ws = _ws(wsb, dw.device)
+    ws = workspace.get(wsb, dw.device)
     call("mopa_spconv_bwd_weight", ptr(nbr), K, A_out, x.p, x.ld, x.C, dout.p, dout.ld, dout.C, ptr(dw),
          int(accumulate), ptr(ws), ws.numel(), stream())
 
@@ -431,7 +427,7 @@ def spconv_bwd_weight_of(geom, kind: str, l: int, x: View, dout: View, dw: torch
             K, A = rt.shape
             if query("mopa_spconv_wgrad_run_wanted", K, A, x.C, dout.C, one):
                 assert dw.shape == (K, x.C, dout.C)
-                ws = _ws(query("mopa_spconv_wgrad_run_workspace_bytes", K, A, x.C, dout.C, one), dw.device)
+                ws = workspace.get(query("mopa_spconv_wgrad_run_workspace_bytes", K, A, x.C, dout.C, one), dw.device)
                 call("mopa_spconv_bwd_weight_run", ptr(buf), K, A, one, swap, x.p, x.ld, x.C, dout.p, dout.ld, dout.C, ptr(dw),
                      int(accumulate), ptr(ws), ws.numel(), stream())
                 return
@@ -461,7 +457,7 @@ def bnrelu_fwd(x: View, y: View, gamma, beta, rmean, rvar, training: bool, stats
     if training and syncbn.active():
         return syncbn.fwd(x, y, gamma, beta, rmean, rvar, BN_MOMENTUM, BN_EPS, LEAK, 1, None, stats)
     wsb = query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     call("mopa_bnrelu_rows_fwd", x.p, x.ld, y.p, y.ld, x.rows, x.C, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
          BN_MOMENTUM, BN_EPS, LEAK, int(training), ptr(stats), ptr(ws), ws.numel(), stream())
 
@@ -475,7 +471,7 @@ def bnrelu_fwd_groups(x: View, y: View, gamma, beta, rmean, rvar, training: bool
     """All row groups of one layer in one set of launches (3 kernels instead of 3 per group); stats: (len(groups), 4, C).  Bit-identical
     to bnrelu_fwd per row range (csrc/rows.hip::BnGroups) -- what the native executor issues too."""
     wsb = query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     s1, s2 = _splits(groups)
     call("mopa_bn_act_fwd_groups", x.p, x.ld, y.p, y.ld, x.rows, x.C, len(groups), s1, s2, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar),
          BN_MOMENTUM, BN_EPS, LEAK, 1, None, 0, int(training), ptr(stats), ptr(ws), ws.numel(), stream())
@@ -483,7 +479,7 @@ def bnrelu_fwd_groups(x: View, y: View, gamma, beta, rmean, rvar, training: bool
 
 def bnrelu_bwd_groups(dy: View, x: View, dx: View, stats, training: bool, dgamma, dbeta, acc_dx: bool, acc_params: bool, groups):
     wsb = query("mopa_bnrelu_rows_bwd_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     s1, s2 = _splits(groups)
     call("mopa_bn_act_bwd_groups", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, len(groups), s1, s2, ptr(stats), LEAK, 1,
          None, 0, None, 0, 0, int(training), ptr(dgamma), ptr(dbeta), int(acc_params), int(acc_dx), ptr(ws), ws.numel(), stream())
@@ -494,7 +490,7 @@ def bnrelu_bwd(dy: View, x: View, dx: View, stats, training: bool, dgamma, dbeta
     if gathered is not None:   # the forward pass of this layer ran with global statistics
         return syncbn.bwd(dy, x, dx, stats, LEAK, 1, None, None, False, dgamma, dbeta, acc_params, acc_dx, gathered)
     wsb = query("mopa_bnrelu_rows_bwd_workspace_bytes", x.rows, x.C)
-    ws = _ws(wsb, x.t.device)
+    ws = workspace.get(wsb, x.t.device)
     call("mopa_bnrelu_rows_bwd", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, ptr(stats), LEAK, int(training),
          ptr(dgamma), ptr(dbeta), int(acc_params), int(acc_dx), ptr(ws), ws.numel(), stream())
 
@@ -820,7 +816,7 @@ def _native_forward(ctx, spec, geom, training, feats, flat, P, prog):
         if not hasattr(geom, "_ws_bytes"):
             geom._ws_bytes = {}
         wsb = geom._ws_bytes[key] = int(_lib.load().mopa_scn_workspace_bytes(nt["prog"].ctypes.data, len(nt["prog"]), gd.ctypes.data, C, m))
-    ws = _ws(wsb, dev)
+    ws = workspace.get(wsb, dev)
     call("mopa_scn_forward", nt["prog"].ctypes.data, len(nt["prog"]), nat.params.ctypes.data, nat.forms.ctypes.data, gd.ctypes.data,
          bufs.ctypes.data, io.ctypes.data, ptr(ws), ws.numel(), stream())
     ctx.native = (nat, bufs, arena, io, wsb)
@@ -871,12 +867,12 @@ def _native_backward(ctx, dfeats, dl1, dl2):
     elif nt["stem_step"] >= 0:
         plan = plan.copy()
         plan[nt["stem_step"], 9] = 1      # no gradient w.r.t. the input features: the stem's backward-data is skipped
-    ws = _ws(wsb, dev)
+    ws = workspace.get(wsb, dev)
     side = _wgrad3_side(dev)
     if side is not None:
         wst, ev_ready, ev_done = side
         with torch.cuda.stream(wst):
-            ws2 = _ws(wsb, dev)    # the second stream's own scratch (keyed by stream)
+            ws2 = workspace.get(wsb, dev)    # the second stream's own scratch (keyed by stream)
         io[_IO["WSTREAM"]], io[_IO["WS2"]], io[_IO["WS2_BYTES"]] = wst.cuda_stream, ws2.data_ptr(), ws2.numel()
         io[_IO["EV_READY"]], io[_IO["EV_DONE"]] = ev_ready.cuda_event, ev_done.cuda_event
     call("mopa_scn_backward", prog_t.ctypes.data, len(prog_t), plan.ctypes.data, len(plan), nat.params.ctypes.data, nat.forms.ctypes.data,
@@ -1009,7 +1005,7 @@ class SCNNetFunction(torch.autograd.Function):
         dl2 = cont(dl2) if (spec.dual_head and dl2 is not None and dl2.numel()) else None
         dy = gview(out_ref)
         wsb = query("mopa_output_layer_heads_bwd_workspace_bytes", N, m, C)
-        ws = _ws(wsb, dev)
+        ws = workspace.get(wsb, dev)
         hnames = (["linear.weight", "linear.bias"] if dl1 is not None else []) + \
                  (["linear2.weight", "linear2.bias"] if dl2 is not None else [])
         hg, hacc = sink.take(*hnames)

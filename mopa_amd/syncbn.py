@@ -54,10 +54,6 @@ class local_statistics:
         return False
 
 
-def _ws(nbytes, dev):
-    return workspace.get(max(int(nbytes), 256), dev)
-
-
 def fwd(x, y, gamma, beta, rmean, rvar, momentum, eps, leak, act, res, stats):
     """Training-mode forward of one BatchNorm(+residual)(+ReLU) with global statistics.  Returns the gathered moments
     ``[world][2C+1]`` (double) -- the backward pass reads the global row count from them."""
@@ -75,7 +71,7 @@ def fwd(x, y, gamma, beta, rmean, rvar, momentum, eps, leak, act, res, stats):
         call("mopa_bn_act_fwd_sync", x.p, x.ld, y.p, y.ld, 0, C, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), momentum, eps,
              leak, int(act), None, 0, ptr(gathered), world, ptr(stats), stream())
         return gathered
-    ws = _ws(query("mopa_bnrelu_rows_workspace_bytes", x.rows, C), dev)
+    ws = workspace.get(query("mopa_bnrelu_rows_workspace_bytes", x.rows, C), dev)
     mine = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
     call("mopa_bn_sync_moments", x.p, x.ld, x.rows, C, ptr(mine), ptr(ws), ws.numel(), stream())
     dist.all_gather_into_tensor(gathered, mine, group=group)
@@ -95,7 +91,7 @@ def bwd(dy, x, dx, stats, leak, act, ymask, dres, acc_dres, dgamma, dbeta, acc_p
             dgamma.zero_()
             dbeta.zero_()
         return
-    ws = _ws(query("mopa_bnrelu_rows_workspace_bytes", x.rows, C), dev)
+    ws = workspace.get(query("mopa_bnrelu_rows_workspace_bytes", x.rows, C), dev)
     sums = torch.empty(2 * C, dtype=torch.float64, device=dev)
     call("mopa_bn_sync_bwd_sums", dy.p, dy.ld, x.p, x.ld, x.rows, C, ptr(stats), leak, int(act),
          ymask.p if ymask is not None else None, ymask.ld if ymask is not None else 0, ptr(dgamma), ptr(dbeta), int(acc_params),

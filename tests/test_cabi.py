@@ -19,6 +19,30 @@ def _protos():
     return out
 
 
+# this file's own reading of a C parameter (not the generator's): the binding's letter for each scalar type
+_LETTERS = {"int": "i", "int32_t": "i", "int64_t": "l", "uint64_t": "u", "size_t": "z", "float": "f", "double": "d"}
+
+
+def _header_signatures():
+    """name -> (return letter, argument letters) read from include/mopa_hip.h: a parameter with a `*` is a pointer, any other
+    one is `[const] <scalar type> <name>` with a scalar type of _LETTERS."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    out = {}
+    for m in re.finditer(r"\b(int|size_t)\s+(mopa_\w+)\s*\(([^;]*)\)\s*;", src):
+        letters = ""
+        for a in m.group(3).split(","):
+            words = [w for w in a.split() if w != "const"]
+            if words in ([], ["void"]):
+                continue
+            if "*" in a:
+                letters += "p"
+            else:
+                assert len(words) == 2 and words[0] in _LETTERS, (m.group(2), a)
+                letters += _LETTERS[words[0]]
+        out[m.group(2)] = (_LETTERS[m.group(1)], letters)
+    return out
+
+
 def test_header_lists_the_whole_abi():
     protos = _protos()
     assert len(protos) >= 49
@@ -47,7 +71,28 @@ def test_python_binding_matches_header():
         ctype, nargs = protos[name]
         assert len(args) == nargs, (name, len(args), nargs)
         assert (res == "z") == (ctype == "size_t"), name
-    _lib.load()  # sets argtypes on every symbol
+    want = _header_signatures()
+    for name in protos:
+        assert tuple(_lib.SIGNATURES[name]) == want[name], (name, _lib.SIGNATURES[name], want[name])
+    lib = _lib.load()  # sets argtypes on every symbol
+    ctype_of = {"p": ctypes.c_void_p, "i": ctypes.c_int32, "l": ctypes.c_int64, "u": ctypes.c_uint64, "z": ctypes.c_size_t,
+                "f": ctypes.c_float, "d": ctypes.c_double}
+    for name, (res, args) in want.items():
+        fn = getattr(lib, name)
+        assert fn.restype is ctype_of[res] and list(fn.argtypes) == [ctype_of[a] for a in args], name
+
+
+def test_generated_files_are_fresh():
+    """The committed generated files are exactly what csrc/gen_header.py makes of the MOPA_API definitions today."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_header", os.path.join(ROOT, "mopa_amd", "csrc", "gen_header.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    texts = gen.generate()
+    assert sorted(texts) == ["include/mopa_hip.h", "mopa_amd/_abi.py", "mopa_amd/csrc/exec_table.inc"]
+    for path, text in texts.items():
+        with open(os.path.join(ROOT, path)) as f:
+            assert f.read() == text, f"{path} is stale: run mopa_amd/csrc/gen_header.py"
 
 
 def test_workspace_queries_run_on_the_host():
@@ -116,7 +161,8 @@ def test_command_list_executor_table_and_packing():
     # host pointers: which arguments are host pointers comes from the header's `_host` suffix; the stem's fused
     # weight gradient (arg 10 = geom_host) is copied like the other geometries, an entry point with a host table of unknown size
     # is refused instead of recording a raw host address, and a pointer list copies exactly n entries
-    from mopa_amd._host_args import HOST_PARAMS
+    from mopa_amd._abi import HOST_PARAMS
+    assert _lib.HOST_PARAMS is HOST_PARAMS
     src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     seen = 0
     for m in re.finditer(r"\b(?:int|size_t)\s+(mopa_\w+)\s*\(([^;]*)\)\s*;", src):
