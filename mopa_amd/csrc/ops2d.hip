@@ -439,3 +439,51 @@ MOPA_API int mopa_colsum(const float* x, int32_t ld, int64_t num_rows, int32_t C
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }
+
+// ------------------------------------------------------------------------------------------ point indices -> pixel rows
+// Net2DSeg.pack_indices on the device: idx = the batch's (N_b, 2) int64 [row v, col u] image indices one behind the other,
+// off_host[b] .. off_host[b + 1] = the points of image b.  pix[i] = (b * Hp + row) * Wp + col, the row of point i in the
+// /16-padded NHWC feature map.  An index outside its H x W image is clamped into that image (the gather behind it stays inside
+// the map) and counted in status[0]; the caller decides whether to read the count back.  One thread per point, one 16-byte load
+// of the pair; the only atomic is the integer count, one per wave that saw a bad index.
+#define PP_MAXB 32
+struct PackOffsets { int64_t off[PP_MAXB + 1]; };
+__global__ __launch_bounds__(256) void k_pack_point_pix(const longlong2* __restrict__ idx, PackOffsets o, int B, int H, int W, int Hp,
+                                                        int Wp, int32_t* __restrict__ pix, int32_t* __restrict__ status) {
+  const int64_t n = o.off[B];
+  for (int64_t i0 = (int64_t)blockIdx.x * blockDim.x; i0 < n; i0 += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = i0 + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+      int b = 0;
+      while (b + 1 < B && i >= o.off[b + 1]) ++b;   // (empty images are skipped: their range holds no i)
+      const longlong2 rc = idx[i];
+      bad = rc.x < 0 || rc.x >= H || rc.y < 0 || rc.y >= W;
+      const int r = (int)(rc.x < 0 ? 0 : (rc.x >= H ? H - 1 : rc.x));
+      const int c = (int)(rc.y < 0 ? 0 : (rc.y >= W ? W - 1 : rc.y));
+      pix[i] = (b * Hp + r) * Wp + c;
+    }
+    const unsigned long long m = __ballot(bad);
+    if (m && (threadIdx.x & (warpSize - 1)) == 0) atomicAdd(status, __popcll(m));
+  }
+}
+MOPA_API int mopa_pack_point_pix(const int64_t* idx, const int64_t* off_host, int32_t B, int32_t H, int32_t W, int32_t* pix,
+                                 int32_t* status, void* stream) {
+  if (!off_host || !status || B < 1 || B > PP_MAXB || H < 1 || W < 1) return MOPA_ERR_ARG;
+  const int64_t Hp = (H + 15) / 16 * 16, Wp = (W + 15) / 16 * 16;
+  if ((int64_t)B * Hp * Wp > 0x7FFFFFFFll) return MOPA_ERR_ARG;   // pixel rows are int32
+  PackOffsets o;
+  if (off_host[0] != 0) return MOPA_ERR_ARG;
+  for (int b = 0; b <= B; ++b) {
+    if (b && off_host[b] < off_host[b - 1]) return MOPA_ERR_ARG;
+    o.off[b] = off_host[b];
+  }
+  for (int b = B + 1; b <= PP_MAXB; ++b) o.off[b] = off_host[B];
+  const int64_t n = off_host[B];
+  if (n && (!idx || !pix || ((uintptr_t)idx & 15))) return MOPA_ERR_ARG;
+  if (hipMemsetAsync(status, 0, sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return MOPA_ERR_LAUNCH;
+  if (n == 0) return MOPA_OK;
+  k_pack_point_pix<<<stream_grid(n, 256), 256, 0, (hipStream_t)stream>>>((const longlong2*)idx, o, B, H, W, (int)Hp, (int)Wp, pix, status);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}

@@ -100,16 +100,16 @@ def _refresh_stale_forms(st):
     step, each of which used to be an 8-10 us kernel serialised on the main stream at the layer's first use after the
     optimizer step.  The cached destination tensors are re-used (same sizes; their readers are ahead on the same stream).
     A form that was never built on this stream still takes the single-kernel path."""
-    from ._lib import WEIGHTS_EPOCH
-    epoch = WEIGHTS_EPOCH[0]
+    epoch = _lib.weights_epoch()
+    cache = _relayout_cache if _lib.FORM_SCOPE is None else _lib.FORM_SCOPE.forms2d
     rows, hits = [], []
-    for key, ent in list(_relayout_cache.items()):
+    for key, ent in list(cache.items()):
         if key[2] != st or len(ent) < 4 or ent[3] is None:
             continue
         tag, t, wref, meta = ent
         w = wref()
         if w is None:
-            del _relayout_cache[key]
+            del cache[key]
             continue
         new_tag = (epoch, w._version, w.data_ptr())
         if tag == new_tag:
@@ -120,7 +120,7 @@ def _refresh_stale_forms(st):
         desc = np.asarray(rows[i:i + 48], dtype=np.int64)
         call("mopa_conv2d_weight_forms_batched", desc.ctypes.data, len(desc), st)
     for key, new_tag, t, wref, meta in hits:
-        _relayout_cache[key] = (new_tag, t, wref, meta)
+        cache[key] = (new_tag, t, wref, meta)
 
 
 def _cached_weight_form(w, form, build, meta=None):
@@ -131,30 +131,31 @@ def _cached_weight_form(w, form, build, meta=None):
     made it).  `meta` = (O, I, KH, KW, kind, arg) of mopa_conv2d_weight_forms_batched lets a later refresh rebuild the form
     together with all other stale ones."""
     import weakref
-    from ._lib import WEIGHTS_EPOCH
+    scope = _lib.FORM_SCOPE   # (mopa_amd.teacher: the forms of the EMA weights live in the teacher's own dictionaries, keyed on FlatEMA.version)
+    cache, refreshed = (_relayout_cache, _refreshed) if scope is None else (scope.forms2d, scope.refreshed2d)
     if _CAPTURE is not None:
         # launches are being recorded into a HIP graph (Graph2D below): hand out the form that the replaying stream owns and record
         # nothing -- Graph2D.replay brings every form of that stream up to date (one batched launch) before each replay
-        hit = _relayout_cache.get((id(w), form, _CAPTURE))
+        hit = cache.get((id(w), form, _CAPTURE))
         if hit is None or hit[2]() is not w:
             raise _CaptureMiss(f"weight form {form} of a {tuple(w.shape)} weight was never built on the replaying stream")
         return hit[1]
     st = stream()
     key = (id(w), form, st)
-    tag = (WEIGHTS_EPOCH[0], w._version, w.data_ptr())
-    hit = _relayout_cache.get(key)
+    tag = (_lib.weights_epoch(), w._version, w.data_ptr())
+    hit = cache.get(key)
     if hit is not None and hit[0] == tag and hit[2]() is w:
         return hit[1]
-    if hit is not None and hit[2]() is w and BATCHED_REFRESH and _refreshed.get(st) != tag[0]:
-        _refreshed[st] = tag[0]      # once per epoch and stream
+    if hit is not None and hit[2]() is w and BATCHED_REFRESH and refreshed.get(st) != tag[0]:
+        refreshed[st] = tag[0]      # once per epoch and stream
         _refresh_stale_forms(st)
-        hit = _relayout_cache.get(key)
+        hit = cache.get(key)
         if hit is not None and hit[0] == tag:
             return hit[1]
     t = build()
-    if len(_relayout_cache) > 4096:   # temporaries (tests, one-off calls) must not pile up
-        _relayout_cache.clear()
-    _relayout_cache[key] = (tag, t, weakref.ref(w), meta)
+    if len(cache) > 4096:   # temporaries (tests, one-off calls) must not pile up
+        cache.clear()
+    cache[key] = (tag, t, weakref.ref(w), meta)
     return t
 
 
@@ -685,7 +686,15 @@ def _group(v: Img, g, G):
     return Img(v.t[g * n:(g + 1) * n], v.B // G, v.H, v.W, v.col, v.C)
 
 
-def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=1):
+class _NoTape:
+    """The tape of a pass that will never run backward (mopa_amd.teacher): keeps nothing, so every activation is released -- in a
+    recorded pass: handed back to the key's private pool -- as soon as its last reader has been enqueued."""
+
+    def append(self, rec):
+        pass
+
+
+def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=1, keep_tape=True):
     """UNetResNet34 on a contiguous fp32 (B,3,H,W) image -> (feat, tape, J).  feat: (B, Hp, Wp, 64) NHWC, the /16-padded decoder
     output; tape: what the backward pass walks; J: the join buffers.  Every launch goes to the current stream, nothing is read
     back: the pass can be recorded into a HIP graph (Graph2D).  seed_t: int64 device scalar holding the dropout seed (graph
@@ -701,7 +710,7 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
     G = groups
     seeds = tuple(drop_seed) if isinstance(drop_seed, (tuple, list)) else (drop_seed,) * G
     Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
-    tape = []
+    tape = [] if keep_tape else _NoTape()
     nbt = []   # BatchNorm2d.num_batches_tracked of every layer that ran: bumped together at the end (one launch, not 43)
 
     def bn(name, x, act=1, res=None, out=None, defer=False):
@@ -1089,6 +1098,26 @@ class Graph2D:
         self.dfeat = new_img(self.feat.B, self.feat.H, self.feat.W, 64, self.dev)
         self.ptrs = tuple(t.data_ptr() for t in flat)
         GRAPH_STATS["recorded"] += 1
+
+    def record_eval(self, P, flat):
+        """The forward pass of an eval forward without gradients (mopa_amd.teacher): no tape, no backward list, no dropout seed.
+        What stays pinned in the key's private pool afterwards is the input image, the output feature map and the pool's
+        high-water mark of live activations (not their sum: nothing is kept for a backward pass)."""
+        self.side = torch.cuda.Stream(device=self.dev)
+        self.img = torch.empty(self.B, 3, self.H, self.W, dtype=torch.float32, device=self.dev)
+        self.training, self.drop_p, self.seed_t = False, 0.0, None
+        self.fwd, self.feat = self._record(
+            lambda: _backbone_forward(P, self.img, False, 0.0, 0, None, self.dev, 1, keep_tape=False)[0], None)
+        self.ptrs = tuple(t.data_ptr() for t in flat)
+        GRAPH_STATS["eval_recorded"] = GRAPH_STATS.get("eval_recorded", 0) + 1
+
+    def forward_eval(self, imgc):
+        """Replay the recorded eval forward on `imgc` -> the feature map (valid until the next replay of this key)."""
+        self.img.copy_(imgc)
+        _refresh_stale_forms(stream())
+        self._replay(self.fwd)
+        GRAPH_STATS["eval_replays"] = GRAPH_STATS.get("eval_replays", 0) + 1
+        return self.feat
 
     def params_moved(self, flat):
         return len(flat) != len(self.ptrs) or any(t.data_ptr() != a for t, a in zip(flat, self.ptrs))

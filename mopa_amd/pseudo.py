@@ -65,6 +65,7 @@ class FlatEMA:
         self.opt, self.decay = optimizer, float(decay)
         self.num_updates = 0 if use_num_updates else None
         self.shadow = optimizer.flat.clone()
+        self.version = 0   # bumped by every write to `shadow`: what mopa_amd.teacher keys the shadow's derived weight forms on
 
     def state_dict(self):
         """Same keys as ``torch_ema.ExponentialMovingAverage.state_dict()`` (per-parameter shadow tensors), so EMA
@@ -85,6 +86,7 @@ class FlatEMA:
             raise ValueError("FlatEMA.load_state_dict: %d shadow tensors for %d parameters" % (len(sp), len(self.opt.params)))
         for (off, n), t in zip(self.opt._slices, sp):
             self.shadow[off:off + n].copy_(t.reshape(-1))
+        self.version += 1
 
     def update(self):
         decay = self.decay
@@ -92,6 +94,7 @@ class FlatEMA:
             self.num_updates += 1
             decay = min(decay, (1 + self.num_updates) / (10 + self.num_updates))
         call("mopa_ema_update", ptr(self.shadow), ptr(self.opt.flat), self.shadow.numel(), decay, stream())
+        self.version += 1
 
     @contextlib.contextmanager
     def average_parameters(self):

@@ -310,14 +310,15 @@ def _refresh_stale_forms(st):
     destination buffers are re-used (same sizes; the launches that read them are ahead of this one on the same stream).  A form
     that was never built before (new network, another geometry-dependent plan) still takes the single-kernel path."""
     import numpy as np
-    epoch = _lib.WEIGHTS_EPOCH[0]
+    epoch = _lib.weights_epoch()
+    cache = _weight_cache if _lib.FORM_SCOPE is None else _lib.FORM_SCOPE.forms3d
     rows, hits = [], []
-    for key, (tag, t, wref) in list(_weight_cache.items()):
+    for key, (tag, t, wref) in list(cache.items()):
         if key[2] != st:
             continue
         w = wref()
         if w is None:
-            del _weight_cache[key]
+            del cache[key]
             continue
         new_tag = (epoch, w._version, w.data_ptr())
         if tag == new_tag:
@@ -330,7 +331,7 @@ def _refresh_stale_forms(st):
         desc = np.asarray(rows[i:i + 64], dtype=np.int64)
         call("mopa_spconv_pack_weights_batched", desc.ctypes.data, len(desc), st)
     for key, new_tag, t, wref in hits:
-        _weight_cache[key] = (new_tag, t, wref)
+        cache[key] = (new_tag, t, wref)
 
 
 def _weight_form(w: torch.Tensor, form: tuple) -> torch.Tensor:
@@ -340,14 +341,16 @@ def _weight_form(w: torch.Tensor, form: tuple) -> torch.Tensor:
     import weakref
     st = stream()
     key = (id(w), form, st)
-    tag = (_lib.WEIGHTS_EPOCH[0], w._version, w.data_ptr())
-    hit = _weight_cache.get(key)
+    scope = _lib.FORM_SCOPE   # (mopa_amd.teacher: the forms of the EMA weights live in the teacher's own dictionaries)
+    cache, refreshed = (_weight_cache, _refreshed) if scope is None else (scope.forms3d, scope.refreshed3d)
+    tag = (_lib.weights_epoch(), w._version, w.data_ptr())
+    hit = cache.get(key)
     if hit is not None and hit[0] == tag and hit[2]() is w:
         return hit[1]
-    if hit is not None and hit[2]() is w and _refreshed.get(st) != tag[0] and BATCHED_REPACK:
-        _refreshed[st] = tag[0]      # once per epoch and stream: everything stale goes in one launch
+    if hit is not None and hit[2]() is w and refreshed.get(st) != tag[0] and BATCHED_REPACK:
+        refreshed[st] = tag[0]      # once per epoch and stream: everything stale goes in one launch
         _refresh_stale_forms(st)
-        hit = _weight_cache.get(key)
+        hit = cache.get(key)
         if hit is not None and hit[0] == tag:
             return hit[1]
     K = w.shape[0]
@@ -359,9 +362,9 @@ def _weight_form(w: torch.Tensor, form: tuple) -> torch.Tensor:
         call("mopa_spconv_run_pack_weight", ptr(w), K, w.shape[1], w.shape[2], form[1], ptr(t), stream())
     else:
         t = spconv_transpose_weight(w)
-    if len(_weight_cache) > 4096:
-        _weight_cache.clear()
-    _weight_cache[key] = (tag, t, weakref.ref(w))
+    if len(cache) > 4096:
+        cache.clear()
+    cache[key] = (tag, t, weakref.ref(w))
     return t
 
 
@@ -767,7 +770,7 @@ class NativeState:
                 w = P[name + ".weight"]
                 self.params[i, 0] = w.data_ptr()
                 versions.append(w._version)
-        tag = (_lib.WEIGHTS_EPOCH[0], tuple(versions), int(self.params[:, 0].sum()))
+        tag = (_lib.weights_epoch(), tuple(versions), int(self.params[:, 0].sum()))
         if tag != self._tag:
             self._tag = tag
             self.epoch += 1
