@@ -337,9 +337,10 @@ MOPA_API size_t mopa_mask_cons_workspace_bytes(int32_t B, int32_t HW, int32_t C)
 // state (saved for backward): mu [B][MAXID][C] | cnt [B][MAXID] | nvalid [B]   -> (B*MAXID*(C+1) + B) floats
 MOPA_API size_t mopa_mask_cons_state_floats(int32_t B, int32_t C) { return (size_t)B * MAXID * (C + 1) + B; }
 
+// k_norm = 1 (a one-row image) only without the entropy term: its normaliser log2(k_norm) would be 0.
 MOPA_API int mopa_mask_cons_fwd(const float* probs, const int32_t* masks, int32_t B, int32_t HW, int32_t C, int32_t k_norm,
                                 int32_t min_entropy, float* loss, float* state, void* ws, size_t ws_bytes, void* stream) {
-  if (B <= 0 || HW <= 0 || C <= 0 || C > 32 || k_norm < 2) return MOPA_ERR_ARG;
+  if (B <= 0 || HW <= 0 || C <= 0 || C > 32 || k_norm < 1 || (min_entropy && k_norm < 2)) return MOPA_ERR_ARG;
   if (ws_bytes < mopa_mask_cons_workspace_bytes(B, HW, C)) return MOPA_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int nblk = mc_nblk(HW);
@@ -360,7 +361,7 @@ MOPA_API int mopa_mask_cons_fwd(const float* probs, const int32_t* masks, int32_
 }
 MOPA_API int mopa_mask_cons_bwd(const float* probs, const int32_t* masks, int32_t B, int32_t HW, int32_t C, int32_t k_norm,
                                 int32_t min_entropy, const float* state, const float* gout, float* dprobs, void* stream) {
-  if (B <= 0 || HW <= 0 || C <= 0 || C > 32 || k_norm < 2) return MOPA_ERR_ARG;
+  if (B <= 0 || HW <= 0 || C <= 0 || C > 32 || k_norm < 1 || (min_entropy && k_norm < 2)) return MOPA_ERR_ARG;
   const float* mu = state;
   const float* cnt = mu + (size_t)B * MAXID * C;
   const float* nvalid = cnt + (size_t)B * MAXID;

@@ -5,7 +5,8 @@
 // biases :104-110; mopa/models/xmuda_arch.py:58-60 (full-image head).  Oracle: oracle/net2d.py.
 #include "common.h"
 
-#define PH_MAXNC 16  // classes handled by the full-image head kernels (reference configs: 5 and 10)
+#define PH_MAXNC 16  // register bound of the full-image head kernels' class loops (reference configs: 5 and 10)
+#define PH_LDS_MAX (64 * 1024)
 
 // ------------------------------------------------------------------------------------------ maxpool 3x3 s2 p1
 // y[b][oy][ox][c] = max over the 3x3 window (first maximum in (ky,kx) scan order wins, like torch); idx stores the
@@ -218,7 +219,7 @@ __device__ __forceinline__ float ph_lane_sum(float v, int MQ) {
 __global__ __launch_bounds__(256) void k_pixel_head_fwd(const float* __restrict__ x, int ld, int B, int Hp, int Wp, int H, int W,
                                                          int M, int NC, const float* __restrict__ w, const float* __restrict__ bias,
                                                          float* __restrict__ pred) {
-  const int MQ = M >> 2;                       // lanes per pixel: 4, 8 or 16 (power of two, checked by the launcher)
+  const int MQ = M >> 2;                       // lanes per pixel: a power of two <= 64 (checked by the launcher)
   const int cq = threadIdx.x % MQ;
   float4 wr[PH_MAXNC];
   float bk[PH_MAXNC];
@@ -346,12 +347,23 @@ __global__ __launch_bounds__(256) void k_head_partial_reduce(const float* __rest
   }
 }
 
+// LDS of k_pixel_head_wgrad_partial: one [NC][M+1] slab per pixel lane of the block
+static inline size_t ph_wgrad_lds_bytes(int M, int NC) { return (size_t)(256 / (M >> 2)) * NC * (M + 1) * sizeof(float); }
+// 1 when the full-image head runs (M, num_classes), forward AND backward (one set for both launchers), else 0: M/4 lanes per pixel,
+// a power of two <= 64 that holds every class (lane k writes class k), the class count within the register bound, and the weight
+// gradient's staging buffer within 64 KB of LDS -- at most 15 classes at M = 64, 128 and 256, M/4 classes at M <= 32.
+MOPA_API int mopa_pixel_head_supported(int32_t M, int32_t num_classes) {
+  if (M <= 0 || (M & 3) || num_classes <= 0 || num_classes > PH_MAXNC) return 0;
+  const int MQ = M >> 2;
+  if ((MQ & (MQ - 1)) != 0 || MQ > 64 || MQ < num_classes) return 0;
+  return ph_wgrad_lds_bytes(M, num_classes) <= PH_LDS_MAX ? 1 : 0;
+}
 MOPA_API int mopa_pixel_head_fwd(const float* x, int32_t ld, int32_t B, int32_t Hp, int32_t Wp, int32_t H, int32_t W, int32_t M,
                                  int32_t num_classes, const float* w, const float* bias, float* pred, void* stream) {
-  if (B <= 0 || H <= 0 || W <= 0 || H > Hp || W > Wp || M <= 0 || (M & 3) || num_classes <= 0 || num_classes > PH_MAXNC || ld < M || (ld & 3))
+  if (B <= 0 || H <= 0 || W <= 0 || H > Hp || W > Wp || !mopa_pixel_head_supported(M, num_classes) || ld < M || (ld & 3) ||
+      (((uintptr_t)x | (uintptr_t)w) & 15))
     return MOPA_ERR_ARG;
-  const int MQ = M >> 2;   // lanes per pixel: a power of two <= 64 that holds every class (lane k writes class k)
-  if ((MQ & (MQ - 1)) != 0 || MQ > 64 || MQ < num_classes || (((uintptr_t)x | (uintptr_t)w) & 15)) return MOPA_ERR_ARG;
+  const int MQ = M >> 2;   // lanes per pixel
   k_pixel_head_fwd<<<stream_grid(cdiv64((int64_t)B * H * W, 256 / MQ) * 256, 256), 256, 0, (hipStream_t)stream>>>(
       x, ld, B, Hp, Wp, H, W, M, num_classes, w, bias, pred);
   MOPA_CHECK_LAUNCH();
@@ -364,17 +376,16 @@ MOPA_API int mopa_pixel_head_bwd(const float* dpred, const float* x, int32_t ld,
                                  int32_t W, int32_t M, int32_t num_classes, const float* w, float* dx, int32_t ld_dx,
                                  int32_t accumulate_dx, float* dw, float* db, int32_t accumulate_params, void* ws, size_t ws_bytes,
                                  void* stream) {
-  if (B <= 0 || H <= 0 || W <= 0 || H > Hp || W > Wp || M <= 0 || (M & 3) || 256 % (M >> 2) != 0 || num_classes <= 0 ||
-      num_classes > PH_MAXNC || ld < M || (ld & 3) || ld_dx < M || (ld_dx & 3))
-    return MOPA_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0 || H > Hp || W > Wp || !mopa_pixel_head_supported(M, num_classes) || ld < M || (ld & 3) || ld_dx < M ||
+      (ld_dx & 3))
+    return MOPA_ERR_ARG;   // (every shape check comes before the first launch: a refused call has written nothing)
   if (ws_bytes < mopa_pixel_head_bwd_workspace_bytes(B, H, W, M, num_classes)) return MOPA_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   k_pixel_head_bwd_x<<<stream_grid((int64_t)B * H * W * (M >> 2), 256), 256, (size_t)num_classes * M * sizeof(float), st>>>(
       dpred, B, Hp, Wp, H, W, M, num_classes, w, dx, ld_dx, accumulate_dx);
   const int nblk = (int)cdiv64((int64_t)B * H * W, PH_PIX_PER_BLOCK);
-  const int PL = 256 / (M >> 2);
-  k_pixel_head_wgrad_partial<<<nblk, 256, (size_t)PL * num_classes * (M + 1) * sizeof(float), st>>>(dpred, x, ld, B, Hp, Wp, H, W, M,
-                                                                                                    num_classes, (float*)ws);
+  k_pixel_head_wgrad_partial<<<nblk, 256, ph_wgrad_lds_bytes(M, num_classes), st>>>(dpred, x, ld, B, Hp, Wp, H, W, M, num_classes,
+                                                                                    (float*)ws);
   k_head_partial_reduce<<<32, 256, 0, st>>>((const float*)ws, nblk, M, num_classes, dw, db, accumulate_params);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;

@@ -700,12 +700,29 @@ MOPA_API int mopa_input_layer_bwd(const float* dout, int32_t ld_dout, const int3
 
 // ------------------------------------------------------------------------------------------ OutputLayer + heads
 // feats[p] = y[point_row[p]] (A.3);  logit_h[p] = feats[p] @ W_h^T + b_h for h = 1,2 (xmuda_arch.py:116,124).
-// 16 lanes per point (lane = feature channel group); M = feature width (multiple of 4, <= 64), NC <= 32 classes.
+// 16 lanes per point (lane = feature channel group); M = feature width (multiple of 4, <= 64), NC classes with
+// mopa_heads_supported(M, NC) (below: at most HEAD_MAXNC, and fewer where the backward's staging buffer would not fit).
 // M/4 lanes cooperate on one point: each lane moves one float4 of the row (the gather reads the row once, coalesced,
 // and writes feats once) and holds the partial dot products of its 4 channels with every class row of W1 / W2; a
 // shuffle tree over the lane group finishes the logits.  The lane group is M/4 rounded up to a power of two <= 16 (M = 16: SCN,
 // M = 64: 2D; other multiples of 4 -- UNetSCN(m) with m = 8, 12, 20, ... -- leave the group's last lanes idle).
-#define OH_MAXNC 16
+#define HEAD_MAXNC 16          // register bound: the class loops of the forward and of the weight gradient are unrolled this far
+#define HEAD_PTS_PER_BLOCK 1024
+#define HEAD_LDS_MAX (64 * 1024)
+static inline int head_lanes(int M) {   // lanes per point: M/4 rounded up to a power of two
+  int mqp = 1;
+  while (mqp < (M >> 2)) mqp <<= 1;
+  return mqp;
+}
+// LDS of k_head_wgrad_partial: one [NC][M+1] slab per point lane of the block
+static inline size_t head_wgrad_lds_bytes(int M, int NC) { return (size_t)(256 / head_lanes(M)) * NC * (M + 1) * sizeof(float); }
+// 1 when the point heads run (M, num_classes), forward AND backward (one set for both launchers), else 0: the width a multiple of
+// 4 up to 64, the class count within the register bound, and the weight gradient's staging buffer within 64 KB of LDS -- at most
+// 15 classes at M = 16, 32 and 64, 14 at M = 8, 12 at M = 4, HEAD_MAXNC at the widths whose lane group has idle lanes.
+MOPA_API int mopa_heads_supported(int32_t M, int32_t num_classes) {
+  if (M <= 0 || M > 64 || (M & 3) || num_classes <= 0 || num_classes > HEAD_MAXNC) return 0;
+  return head_wgrad_lds_bytes(M, num_classes) <= HEAD_LDS_MAX ? 1 : 0;
+}
 __global__ __launch_bounds__(256) void k_output_heads_fwd(const float* __restrict__ y, int ld, const int* __restrict__ point_row,
                                                            int N, int M, int NC, const float* __restrict__ w1,
                                                            const float* __restrict__ b1, const float* __restrict__ w2,
@@ -731,7 +748,7 @@ __global__ __launch_bounds__(256) void k_output_heads_fwd(const float* __restric
       *reinterpret_cast<float4*>(feats + (int64_t)p * M + cq * 4) = v;
     }
 #pragma unroll
-    for (int k = 0; k < OH_MAXNC; ++k) {
+    for (int k = 0; k < HEAD_MAXNC; ++k) {
       if (k < NC) {
         const float* wr = lw + k * M + (lane_on ? cq : 0) * 4;   // (an idle lane multiplies zeros)
         float a1 = fmaf(v.x, wr[0], fmaf(v.y, wr[1], fmaf(v.z, wr[2], v.w * wr[3])));
@@ -757,10 +774,8 @@ MOPA_API int mopa_output_layer_heads_fwd(const float* y, int32_t ld_y, const int
                                          int32_t M, int32_t num_classes, const float* w1, const float* b1,
                                          const float* w2, const float* b2, float* feats, float* logit1, float* logit2,
                                          void* stream) {
-  if (n_points <= 0 || M <= 0 || M > 64 || (M & 3) || num_classes <= 0 || num_classes > OH_MAXNC || ld_y < M || (ld_y & 3))
-    return MOPA_ERR_ARG;
-  int mq = 1;
-  while (mq < (M >> 2)) mq <<= 1;
+  if (n_points <= 0 || !mopa_heads_supported(M, num_classes) || ld_y < M || (ld_y & 3)) return MOPA_ERR_ARG;
+  const int mq = head_lanes(M);
   const size_t sh = (size_t)(2 * num_classes * M + 2 * num_classes) * sizeof(float);
   k_output_heads_fwd<<<stream_grid((int64_t)n_points * mq, 256), 256, sh, (hipStream_t)stream>>>(
       y, ld_y, point_row, n_points, M, num_classes, w1, b1, w2, b2, feats, logit1, logit2);
@@ -831,9 +846,7 @@ __global__ __launch_bounds__(256) void k_output_heads_bwd_rows(const float* __re
 
 // Head parameter grads: dW[k][c] = sum_p dl[p][k] * feats[p][c], db[k] = sum_p dl[p][k].  Thread = (point lane,
 // channel quad); block partials [nblk][NC][M+1] then an ordered reduction (deterministic).
-#define HEAD_PTS_PER_BLOCK 1024
-#define HEAD_MAXNC 32
-template <int NCM>   // NCM: compile-time bound of the class count (8 or NCM): the accumulators are NCM x 4 registers
+template <int NCM>   // NCM: compile-time bound of the class count, 8 or HEAD_MAXNC: the accumulators are NCM x 4 registers
 __global__ __launch_bounds__(256) void k_head_wgrad_partial(const float* __restrict__ dl, const float* __restrict__ feats, int N,
                                                              int M, int NC, float* __restrict__ partial) {
   extern __shared__ float red[];  // [PL][NC][M+1]
@@ -926,19 +939,16 @@ MOPA_API int mopa_output_layer_heads_bwd(const float* dfeats, const float* dl1, 
                                          int32_t num_classes, float* dy, int32_t ld_dy, float* dw1, float* db1,
                                          float* dw2, float* db2, int32_t accumulate, void* ws, size_t ws_bytes,
                                          void* stream) {
-  if (n_points <= 0 || num_rows <= 0 || M <= 0 || M > 64 || (M & 3) || num_classes <= 0 || num_classes > HEAD_MAXNC || ld_dy < M ||
-      (ld_dy & 3) || (((uintptr_t)dy | (uintptr_t)dfeats) & 15))
-    return MOPA_ERR_ARG;
-  int mqp = 1;
-  while (mqp < (M >> 2)) mqp <<= 1;
+  if (n_points <= 0 || num_rows <= 0 || !mopa_heads_supported(M, num_classes) || ld_dy < M || (ld_dy & 3) ||
+      (((uintptr_t)dy | (uintptr_t)dfeats) & 15))
+    return MOPA_ERR_ARG;   // (every shape check comes before the first launch: a refused call has written nothing)
   if (ws_bytes < mopa_output_layer_heads_bwd_workspace_bytes(n_points, M, num_classes)) return MOPA_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   k_output_heads_bwd_rows<<<stream_grid(cdiv64((int64_t)num_rows * (M >> 2), 4), 256), 256, (size_t)2 * num_classes * M * sizeof(float), st>>>(
       dfeats, dl1, dl2, w1, w2, row_start, row_points, num_rows, M, num_classes, dy, ld_dy);
   const int nblk = (int)cdiv64(n_points, HEAD_PTS_PER_BLOCK);
   float* partial = (float*)ws;
-  const size_t hsh = (size_t)(256 / mqp) * num_classes * (M + 1) * sizeof(float);
-  if (hsh > 64 * 1024) return MOPA_ERR_ARG;
+  const size_t hsh = head_wgrad_lds_bytes(M, num_classes);   // <= HEAD_LDS_MAX: mopa_heads_supported
   if (dl1 && dw1) {
     if (num_classes <= 8) k_head_wgrad_partial<8><<<nblk, 256, hsh, st>>>(dl1, feats, n_points, M, num_classes, partial);
     else k_head_wgrad_partial<HEAD_MAXNC><<<nblk, 256, hsh, st>>>(dl1, feats, n_points, M, num_classes, partial);

@@ -99,6 +99,31 @@ class _CachedParams:
         self.__dict__["_cache"] = _FlatCache()
 
 
+def head_class_limit(M: int, pixel: bool = False) -> int:
+    """Largest class count the point heads (``pixel``: the full-image head) run at feature width M, forward and backward --
+    what ``mopa_heads_supported`` / ``mopa_pixel_head_supported`` (csrc/rows.hip, csrc/ops2d.hip) answer; 0: no head at that width."""
+    from .._lib import query
+    name = "mopa_pixel_head_supported" if pixel else "mopa_heads_supported"
+    n = 0
+    while query(name, int(M), n + 1):
+        n += 1
+    return n
+
+
+def check_head_classes(who: str, num_classes: int, M: int, pixel: bool = False, width_too: bool = True):
+    """Refuse a class count (or width) the head kernels do not run where the network or its spec is built, not in the middle of a
+    step.  ``width_too=False``: a width without any head passes (UNetSCN states its width limits itself, at the first forward)."""
+    from .._lib import query
+    if query("mopa_pixel_head_supported" if pixel else "mopa_heads_supported", int(M), int(num_classes)):
+        return
+    kind = "full-image" if pixel else "point"
+    limit = head_class_limit(M, pixel)
+    if limit:
+        raise ValueError(f"{who}: {num_classes} classes at feature width {M}; the {kind} head kernels take 1..{limit} classes at that width")
+    if width_too:
+        raise ValueError(f"{who}: feature width {M}; the {kind} head kernels take no class count at that width")
+
+
 def _require_cuda(module: nn.Module):
     dev = next(module.parameters()).device
     if dev.type != "cuda":
@@ -114,8 +139,9 @@ class Net2DSeg(_CachedParams, nn.Module):
         if backbone_2d != "UNetResNet34":
             raise NotImplementedError("2D backbone {} not supported".format(backbone_2d))
         self.net_2d = UNetResNet34(**dict(backbone_2d_kwargs))
-        feat_channels = 64
+        self.feat_channels = feat_channels = 64
         self.num_classes = num_classes
+        self.check_heads()
         self.linear = nn.Linear(feat_channels, num_classes)
         self.output_all = output_all
         self.dual_head = dual_head
@@ -123,6 +149,11 @@ class Net2DSeg(_CachedParams, nn.Module):
             self.linear2 = nn.Linear(feat_channels, num_classes)
         self._cache = _FlatCache()
         self._calls = 0
+
+    def check_heads(self, width_too=True):
+        """The class count against both heads of this network (constructor, every spec; mopa_amd.teacher)."""
+        check_head_classes("Net2DSeg", self.num_classes, self.feat_channels, width_too=width_too)
+        check_head_classes("Net2DSeg", self.num_classes, self.feat_channels, pixel=True, width_too=width_too)
 
     @staticmethod
     def pack_indices(img_indices, H, W, device):
@@ -164,6 +195,7 @@ class Net2DSeg(_CachedParams, nn.Module):
             raise ValueError(f"bn_groups={groups}: at most 3 groups per pass (source, target and one more batch); call the network once per "
                              "group, or in passes of up to three groups")
         # graphs: where dense2d keeps the recorded HIP graphs of the backbone (dropped with the cache when tensor objects change)
+        self.check_heads()   # (the spec is built here: `num_classes` / `linear` may have been replaced since the constructor)
         spec = _Spec(order=order, num_classes=self.num_classes, dual_head=bool(self.dual_head), graphs=self._cache,
                      grad_enabled=torch.is_grad_enabled(), groups=groups)
         seeds = []
@@ -196,6 +228,7 @@ class Net3DSeg(_CachedParams, nn.Module):
         self.net_3d = UNetSCN(**dict(backbone_3d_kwargs))
         m = self.net_3d.out_channels
         self.num_classes = num_classes
+        self.check_heads(width_too=False)   # (UNetSCN constructs widths it does not run and says so at the first forward)
         self.linear = nn.Linear(m, num_classes)
         self.dual_head = dual_head
         if dual_head:
@@ -205,9 +238,14 @@ class Net3DSeg(_CachedParams, nn.Module):
             self.linear3 = nn.Linear(m, num_classes)
         self._cache = _FlatCache()
 
+    def check_heads(self, width_too=True):
+        """The class count against the point heads at this network's width (constructor, every spec; mopa_amd.teacher)."""
+        check_head_classes("Net3DSeg", self.num_classes, self.net_3d.out_channels, width_too=width_too)
+
     def _spec(self):
         order, _ = self._cache.get(self)
         n = self.net_3d
+        self.check_heads()
         return _Spec(order=order, prefix="net_3d.sparseModel.", in_channels=n.in_channels, m=n.m,
                      num_planes=n.num_planes, block_reps=n.block_reps, residual_blocks=n.residual_blocks,
                      num_classes=self.num_classes,

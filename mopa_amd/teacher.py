@@ -160,6 +160,9 @@ class Teacher:
     ``stats``: ``replays`` / ``recorded`` / ``eager`` / ``dropped`` passes of the 2D backbone, ``failed`` recordings."""
 
     def __init__(self, model_2d, model_3d, ema_2d=None, ema_3d=None, replay=True):
+        for m in (model_2d, model_3d):   # the class counts of both passes, before the first of them runs
+            if hasattr(m, "check_heads"):
+                m.check_heads(width_too=False)
         self.b2, self.b3 = _Branch(model_2d, ema_2d), _Branch(model_3d, ema_3d)
         self.replay = bool(replay)
         self.graphs = {}
