@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -248,11 +249,15 @@ def wino4_conv9(cin, cout, role):
     return WINO4_CONV9 and role != "fwd" and cin % 16 == 0 and cout % 64 == 0
 
 
-def wino4_layout(cin, cout, B, H, W, role="fwd"):
-    """Weight form of an F(4x4) layer: 3 / 2 = fragments (one-kernel convolution, second / first form), 1 = transposed (fused GEMM +
-    output transform), 0."""
+F4_FORMS = ("F4", "F4 fused", "F4 one", "F4 one9")   # the algorithm table's names of the F(4x4) forms, by weight layout
+
+
+def wino4_layout(cin, cout, B, H, W, role="fwd", want_v=False):
+    """How an F(4x4) convolution runs = the weight form it takes (wino_weight_cached's `transposed`): 3 / 2 = fragments (one-kernel
+    convolution, second / first form), 1 = transposed (fused GEMM + output transform), 0 = plain (batched GEMMs, output transform).
+    conv_plan and wino_conv both ask here.  want_v: V is wanted as a by-product, which only the first one-kernel form has."""
     if wino4_direct(cin, cout, B, H, W, role):
-        return 3 if wino4_conv9(cin, cout, role) else 2
+        return 3 if wino4_conv9(cin, cout, role) and not want_v else 2
     return int(wino4_fused(cin, cout, B, H, W))
 
 
@@ -275,7 +280,7 @@ def wino_tile(cin, cout, k, s, p, B, H, W, role="fwd"):
 #  transformed operands V / M of one layer are 2.25 x its activations, and the fused kernel addresses one transform point with 32-bit
 #  byte offsets: mopa_wino4_gemm_output refuses T * Cin * 4 >= 2^32)
 F4_MAX_PIXELS = int(os.environ.get("MOPA_WINOGRAD_F4_PIXELS", "3000000"))
-# module-level switches (read once: the algorithm choice is asked ~460 times per forward + backward; tests set the attributes)
+# module-level switches (the environment is read once; conv_plan reads the attributes at every call: tests and bench.py set them)
 WINOGRAD = os.environ.get("MOPA_WINOGRAD", "1") != "0"
 WINOGRAD_WGRAD = os.environ.get("MOPA_CONV2D_MFMA", "1") != "0" and os.environ.get("MOPA_WINOGRAD_WGRAD", "1") != "0"
 # Which passes use F(4x4): all three (round 2; round 1 shipped "dgrad,wgrad").  In the backward passes its rounding error
@@ -296,52 +301,41 @@ F4_ROLES = tuple(r for r in os.environ.get("MOPA_WINOGRAD_F4_ROLES", "fwd,dgrad,
 F4_FWD_MIN_PIXELS = 4096
 
 
-def wino_eligible(cin, cout, k, s, p, B, H, W):
-    return wino_tile(cin, cout, k, s, p, B, H, W) != 0
+def _bn_args(bn):
+    """A deferred BatchNorm (stats, G, c0) as the kernels take it; nothing deferred: NULL, one group, from channel 0."""
+    return (ptr(bn[0]), bn[1], bn[2]) if bn is not None else (None, 1, 0)
 
 
 def wino_conv(x_p, ld_in, B, H, W, cin, cout, U, bias, out_p, ld_out, accumulate=False, F=2, bn_in=None, role="fwd", want_v=True):
-    """out = conv3x3(x) (+ bias) through the input transform -> (F+2)^2 batched GEMMs -> the output transform.
-    U: wino_weight_cached(w, dgrad, F, transposed=(F == 4 and wino4_fused(cin, cout, B, H, W))).
-    bn_in = (stats, G, c0) (F = 4 only): x is a BatchNorm's input and relu(batchnorm(x)) is what gets convolved (LazyImg)."""
-    dev = U.device
-    th, tw = (H + F - 1) // F, (W + F - 1) // F
-    T, NP = B * th * tw, (F + 2) ** 2
+    """out = conv3x3(x) (+ bias) through the input transform -> (F+2)^2 batched GEMMs -> the output transform, or (F = 4) the fused
+    form that wino4_layout names for this shape, role and want_v.  U: wino_weight_cached(w, dgrad, F, transposed=that form).
+    bn_in = (stats, G, c0) (F = 4 only): x is a BatchNorm's input and relu(batchnorm(x)) is what gets convolved (LazyImg).
+    -> V where it reached memory (the one-kernel forms: only the first, as a by-product, when want_v)."""
+    T, NP = B * ((H + F - 1) // F) * ((W + F - 1) // F), (F + 2) ** 2
     sfx = "" if F == 2 else "4"
-    if F == 4 and wino4_direct(cin, cout, B, H, W, role) and wino4_conv9(cin, cout, role) and not want_v:
-        if tuple(U.shape) != (36, cin, cout) or getattr(U, "_mopa_wino_layout", (4, 3)) != (4, 3):
-            raise RuntimeError("wino_conv: the nine-point one-kernel F(4x4) path takes its own fragment form (wino_weight_cached(..., transposed=3))")
-        call("mopa_wino4_conv9", x_p, ld_in, ptr(U), ptr(bias) if bias is not None else None, out_p, ld_out, B, H, W, cin, cout,
-             int(accumulate), ptr(bn_in[0]) if bn_in is not None else None, bn_in[1] if bn_in is not None else 1,
-             bn_in[2] if bn_in is not None else 0, stream())
+    form = wino4_layout(cin, cout, B, H, W, role, want_v) if F == 4 else 0
+    if getattr(U, "_mopa_wino_layout", (F, form)) != (F, form) or (form and tuple(U.shape) != ((36, cout, cin) if form == 1 else (36, cin, cout))):
+        raise RuntimeError(f"wino_conv: this shape, role and want_v take the weight form wino_weight_cached(..., F={F}, transposed={form})")
+    if bn_in is not None and F != 4:
+        raise RuntimeError("wino_conv: a deferred BatchNorm needs the F(4x4) input transform")
+    V = torch.empty(NP * T * cin, dtype=torch.float32, device=U.device) if form < 2 or want_v else None
+    if form == 3:
+        call("mopa_wino4_conv9", x_p, ld_in, ptr(U), ptr(bias), out_p, ld_out, B, H, W, cin, cout, int(accumulate), *_bn_args(bn_in), stream())
         return None
-    if F == 4 and wino4_direct(cin, cout, B, H, W, role):
-        if tuple(U.shape) != (36, cin, cout) or getattr(U, "_mopa_wino_layout", (4, 2)) != (4, 2):
-            raise RuntimeError("wino_conv: the one-kernel F(4x4) path takes the fragment weight form (wino_weight_cached(..., transposed=2))")
-        V = torch.empty(NP * T * cin, dtype=torch.float32, device=dev) if want_v else None   # (a by-product, for the weight gradient)
-        call("mopa_wino4_conv", x_p, ld_in, ptr(U), ptr(bias) if bias is not None else None, out_p, ld_out, B, H, W, cin, cout,
-             int(accumulate), ptr(bn_in[0]) if bn_in is not None else None, bn_in[1] if bn_in is not None else 1,
-             bn_in[2] if bn_in is not None else 0, ptr(V) if V is not None else None, stream())
+    if form == 2:   # (V: a by-product, for the weight gradient)
+        call("mopa_wino4_conv", x_p, ld_in, ptr(U), ptr(bias), out_p, ld_out, B, H, W, cin, cout, int(accumulate), *_bn_args(bn_in), ptr(V), stream())
         return V
-    V = torch.empty(NP * T * cin, dtype=torch.float32, device=dev)
     if bn_in is not None:
-        if F != 4:
-            raise RuntimeError("wino_conv: a deferred BatchNorm needs the F(4x4) input transform")
-        call("mopa_wino4_input_bn", x_p, ld_in, B, H, W, cin, ptr(bn_in[0]), bn_in[1], bn_in[2], ptr(V), stream())
+        call("mopa_wino4_input_bn", x_p, ld_in, B, H, W, cin, *_bn_args(bn_in), ptr(V), stream())
     else:
         call(f"mopa_wino{sfx}_input", x_p, ld_in, B, H, W, cin, ptr(V), stream())
-    if F == 4 and wino4_fused(cin, cout, B, H, W):
-        if tuple(U.shape) != (36, cout, cin) or getattr(U, "_mopa_wino_layout", (4, 1)) != (4, 1):
-            raise RuntimeError("wino_conv: the fused F(4x4) path takes the transposed weight transform (wino_weight_cached(..., transposed=1))")
-        call("mopa_wino4_gemm_output", ptr(V), ptr(U), ptr(bias) if bias is not None else None, out_p, ld_out, B, H, W, cin, cout,
-             int(accumulate), stream())
+    if form == 1:
+        call("mopa_wino4_gemm_output", ptr(V), ptr(U), ptr(bias), out_p, ld_out, B, H, W, cin, cout, int(accumulate), stream())
         return V
-    if getattr(U, "_mopa_wino_layout", (F, 0)) != (F, 0):
-        raise RuntimeError("wino_conv: the batched-GEMM path takes the plain weight transform")
-    M = torch.empty(NP * T * cout, dtype=torch.float32, device=dev)
+    M = torch.empty(NP * T * cout, dtype=torch.float32, device=U.device)
     g1 = _geom(B=1, IH=1, IW=T, OHl=1, OWl=T, OHa=1, OWa=T, TH=1, TW=1, KWF=1, Cin=cin, Cout=cout, ld_in=cin, ld_out=cout)
     igemm_batched(ptr(V), ptr(U), ptr(M), g1, NP, T * cin, cin * cout, T * cout)
-    call(f"mopa_wino{sfx}_output", ptr(M), B, H, W, cout, ptr(bias) if bias is not None else None, out_p, ld_out, int(accumulate), stream())
+    call(f"mopa_wino{sfx}_output", ptr(M), B, H, W, cout, ptr(bias), out_p, ld_out, int(accumulate), stream())
     return V
 
 
@@ -372,15 +366,14 @@ def wino4_wgrad_fused(cin, cout, B, H, W):
 
 def wino_wgrad(x: Img, dout: Img, cin, cout, dw, V=None, accumulate=False, F=2, fused=None):
     """dw (OIHW, [cout][cin][3][3]) (+)= weight gradient of conv3x3(x) given dout, through V = B^T x B (kept from the forward
-    pass when the caller has it), dM = A dout A^T -- or, for the layers wino4_wgrad_fused names (fused=None: ask it), in one kernel
-    from x and dout."""
+    pass when the caller has it), dM = A dout A^T -- or, for the layers wino4_wgrad_fused names (fused=None: ask it; ConvOp passes its
+    plan's answer), in one kernel from x and dout."""
     dev = dw.device
     B, H, W = x.B, x.H, x.W
     if F == 4 and V is None and (wino4_wgrad_fused(cin, cout, B, H, W) if fused is None else fused):
-        bn = getattr(x, "bn", None)
         ws = workspace.get(query("mopa_wino4_wgrad_fused_workspace_bytes", B, H, W, cin, cout), dev)
-        call("mopa_wino4_wgrad_fused", x.p, x.ld, ptr(bn[0]) if bn is not None else None, bn[1] if bn is not None else 1,
-             bn[2] if bn is not None else 0, dout.p, dout.ld, B, H, W, cin, cout, ptr(dw), int(accumulate) | 2, ptr(ws), ws.numel(), stream())
+        call("mopa_wino4_wgrad_fused", x.p, x.ld, *_bn_args(getattr(x, "bn", None)), dout.p, dout.ld, B, H, W, cin, cout, ptr(dw),
+             int(accumulate) | 2, ptr(ws), ws.numel(), stream())
         return
     T, NP = B * ((H + F - 1) // F) * ((W + F - 1) // F), (F + 2) ** 2
     sfx = "" if F == 2 else "4"
@@ -388,7 +381,7 @@ def wino_wgrad(x: Img, dout: Img, cin, cout, dw, V=None, accumulate=False, F=2, 
     if V is None:
         V = torch.empty(NP * T * cin, dtype=torch.float32, device=dev)
         if hasattr(x, "bn"):   # a deferred BatchNorm (LazyImg): applied on the way in, as the forward pass did
-            call("mopa_wino4_input_bn", x.p, x.ld, B, H, W, cin, ptr(x.bn[0]), x.bn[1], x.bn[2], ptr(V), stream())
+            call("mopa_wino4_input_bn", x.p, x.ld, B, H, W, cin, *_bn_args(x.bn), ptr(V), stream())
         else:
             call(f"mopa_wino{sfx}_input", x.p, x.ld, B, H, W, cin, ptr(V), stream())
     call(f"mopa_wino{sfx}_dout", dout.p, dout.ld, B, H, W, cout, ptr(dM), stream())
@@ -477,14 +470,43 @@ def join_wgrad_stream(dev):
 
 
 # ------------------------------------------------------------------------------------------------ conv wrappers
-def forward_role(cin, cout, k, s, p, B, H, W, keep_v):
-    """(does the weight gradient of this forward pass want V again?, the role the forward convolution is dispatched under).  V is not
-    wanted when the weight gradient runs in one kernel from x and dY (wino4_wgrad_fused): the training forward pass then keeps nothing
-    and is dispatched like a forward pass without gradients ("fwd_eval")."""
+class ConvPlan(NamedTuple):
+    """What a convolution runs as in each pass, in the algorithm table's words (profiles/algo_table.py): "direct" (implicit GEMM), "F2",
+    and the F(4x4) forms of F4_FORMS.  The layouts are wino_weight_cached's `transposed` (0 for "direct" / "F2")."""
+    fwd: str
+    fwd_layout: int
+    fwd_role: str       # what wino_conv is told: "fwd" or, when nothing is kept, "fwd_eval"
+    keeps_v: bool       # the forward pass hands V to the tape, for the weight gradient
+    takes_lazy: bool    # the input may be a LazyImg (deferred BatchNorm)
+    wgrad: str          # without a V from the forward pass: "direct", "F2", "F4", "F4 one" (one kernel from x and dY)
+    wgrad_F: int        # its tile, 0 / 2 / 4 (a V from the forward pass always goes to the two-operand form of that tile)
+    dgrad: str          # backward-data: the same convolution with the channels swapped, role "dgrad"
+    dgrad_layout: int
+
+
+def conv_plan(cin, cout, k, s, p, B, H, W, training) -> ConvPlan:
+    """The one place where the measured leaf rules are combined; everything else reads the fields.  Not cached: the module-level
+    switches are read at every call.  V is kept exactly when the weight gradient will take it (same tile, and not the one-kernel form,
+    which reads x and dY: that layer's training forward pass is dispatched like one without gradients).  A LazyImg needs the F(4x4)
+    input transform to apply the BatchNorm and, in training, an F(4x4) weight gradient to apply it again."""
     a = (cin, cout, k, s, p, B, H, W)
-    F = wino_tile(*a, "fwd")
-    v_wanted = bool(keep_v and F == 4 and wino_tile(*a, "wgrad") == 4 and wino_wgrad_eligible(*a) and not wino4_wgrad_fused(cin, cout, B, H, W))
-    return v_wanted, ("fwd" if v_wanted or (keep_v and F != 4) else "fwd_eval")
+    Ff, Fw, Fd = wino_tile(*a, "fwd"), wino_tile(*a, "wgrad"), wino_tile(cout, cin, k, s, p, B, H, W, "dgrad")
+    wg = wino_wgrad_eligible(*a)
+    one = wg and Fw == 4 and wino4_wgrad_fused(cin, cout, B, H, W)
+    keeps_v = bool(training and wg and Ff != 0 and Ff == Fw and not one)
+    fwd_role = "fwd" if keeps_v or (training and Ff != 4) else "fwd_eval"
+    fwd_layout = wino4_layout(cin, cout, B, H, W, fwd_role) if Ff == 4 else 0
+    dgrad_layout = wino4_layout(cout, cin, B, H, W, "dgrad") if Fd == 4 else 0
+    return ConvPlan(fwd=F4_FORMS[fwd_layout] if Ff == 4 else ("direct", "F2")[Ff // 2], fwd_layout=fwd_layout, fwd_role=fwd_role, keeps_v=keeps_v,
+                    takes_lazy=bool(Ff == 4 and (not training or (Fw == 4 and wg))),
+                    wgrad="direct" if not wg else "F2" if Fw == 2 else "F4 one" if one else "F4", wgrad_F=Fw if wg else 0,
+                    dgrad=F4_FORMS[dgrad_layout] if Fd == 4 else ("direct", "F2")[Fd // 2], dgrad_layout=dgrad_layout)
+
+
+def forward_role(cin, cout, k, s, p, B, H, W, keep_v):
+    """(does an F(4x4) forward pass keep V?, the role it is dispatched under): a view of conv_plan."""
+    plan = conv_plan(cin, cout, k, s, p, B, H, W, keep_v)
+    return plan.keeps_v and plan.fwd in F4_FORMS, plan.fwd_role
 
 
 class ConvOp:
@@ -502,30 +524,20 @@ class ConvOp:
                      IX0=-self.p, TH=self.k, TW=self.k, KWF=self.k, Cin=self.I, Cout=self.O, ld_in=x.ld, ld_out=out.ld)
 
     def takes_lazy(self, B, H, W, training):
-        """May the input be a LazyImg?  The forward pass must be F(4x4) (the input transform applies the BatchNorm) and, in
-        training, the weight gradient must run on the V kept from it -- nothing else of this layer reads the input."""
-        a = (self.I, self.O, self.k, self.s, self.p, B, H, W)
-        return (wino_tile(*a, "fwd") == 4
-                and (not training or (wino_tile(*a, "wgrad") == 4 and wino_wgrad_eligible(*a))))
+        """May the input be a LazyImg?  (conv_plan)"""
+        return conv_plan(self.I, self.O, self.k, self.s, self.p, B, H, W, training).takes_lazy
 
     def forward(self, x: Img, out: Img, keep_v: bool = False):
         """-> the transformed input V when the Winograd path ran and the weight gradient will want it again (training)."""
-        F = wino_tile(self.I, self.O, self.k, self.s, self.p, x.B, x.H, x.W, "fwd")
-        a = (self.I, self.O, self.k, self.s, self.p, x.B, x.H, x.W)
-        # does the weight gradient of this pass want V again?  Not when it runs in one kernel from x and dY (wino4_wgrad_fused): the
-        # training forward pass then keeps nothing, like a forward pass without gradients
-        v_wanted, drole = forward_role(*a, keep_v)
+        plan = conv_plan(self.I, self.O, self.k, self.s, self.p, x.B, x.H, x.W, keep_v)
         lazy = getattr(x, "bn", None)
-        if lazy is not None and not self.takes_lazy(x.B, x.H, x.W, keep_v):
+        if lazy is not None and not plan.takes_lazy:
             raise RuntimeError("ConvOp.forward: this layer cannot consume a deferred BatchNorm (ask takes_lazy first)")
-        if F:
-            V = wino_conv(x.p, x.ld, x.B, x.H, x.W, self.I, self.O,
-                          wino_weight_cached(self.w, False, F, wino4_layout(self.I, self.O, x.B, x.H, x.W, drole) if F == 4 else 0), self.b, out.p,
-                          out.ld, F=F, bn_in=lazy, role=drole, want_v=v_wanted)
-            if F == 4 and not v_wanted:
-                return None
-            same = F == wino_tile(*a, "wgrad")   # V serves the weight gradient
-            return V if V is not None and keep_v and same and wino_wgrad_eligible(*a) else None
+        if plan.fwd != "direct":
+            F = int(plan.fwd[1])   # "F2", "F4 ..."
+            V = wino_conv(x.p, x.ld, x.B, x.H, x.W, self.I, self.O, wino_weight_cached(self.w, False, F, plan.fwd_layout), self.b, out.p,
+                          out.ld, F=F, bn_in=lazy, role=plan.fwd_role, want_v=plan.keeps_v)
+            return V if plan.keeps_v else None
         wl = relayout_cached(self.w, (self.k, self.k, self.I, self.O), self.O, self.I, self.k, self.k, 0)
         igemm(x.p, wl, self.b, out.p, self._fwd_geom(x, out))
 
@@ -534,26 +546,25 @@ class ConvOp:
         """wgrad_side: the caller joins the weight-gradient stream itself (join_wgrad_stream) after the whole backward pass."""
         dev = self.w.device
         k, s, p = self.k, self.s, self.p
-        if hasattr(x, "bn") and V is None and not (wino_wgrad_eligible(self.I, self.O, k, s, p, x.B, x.H, x.W)
-                                                   and wino_tile(self.I, self.O, k, s, p, x.B, x.H, x.W, "wgrad") == 4):
+        plan = conv_plan(self.I, self.O, k, s, p, x.B, x.H, x.W, True)   # (decided afresh from the switches as they are now)
+        if hasattr(x, "bn") and V is None and plan.wgrad_F != 4:
             raise RuntimeError("ConvOp.backward: the input was a deferred BatchNorm and this layer's weight gradient cannot apply it")
         # weight gradient: the split-K reduction writes (or accumulates into) the OIHW gradient tensor directly.  It depends on x
         # and dout only and nothing downstream of this layer waits for it: it runs on the weight-gradient stream, beside the
         # backward-data chain that the rest of the backward pass is waiting for (Net2DFunction.backward joins the stream).
         ws = wgrad_stream(dev) if wgrad_side else None
         with _on(ws, dout.t):   # (dout is dropped by the caller before the join; x, V, dw, db outlive it)
-            if wino_wgrad_eligible(self.I, self.O, k, s, p, x.B, x.H, x.W):
-                wino_wgrad(x, dout, self.I, self.O, dw, V, accumulate=acc_params, F=wino_tile(self.I, self.O, k, s, p, x.B, x.H, x.W, "wgrad"))
+            if plan.wgrad_F:
+                wino_wgrad(x, dout, self.I, self.O, dw, V, accumulate=acc_params, F=plan.wgrad_F, fused=plan.wgrad == "F4 one")
             else:
                 wgrad(x.p, dout.p, ptr(dw), self._fwd_geom(x, dout), dev, accumulate=acc_params, oihw=True)
             if db is not None:
                 colsum(dout, db, accumulate=acc_params)
         if dx is None:
             return
-        F = wino_tile(self.O, self.I, k, s, p, x.B, x.H, x.W, "dgrad")   # backward-data of a stride-1 3x3 conv is one, too
-        if F:
-            wino_conv(dout.p, dout.ld, x.B, x.H, x.W, self.O, self.I,
-                      wino_weight_cached(self.w, True, F, wino4_layout(self.O, self.I, x.B, x.H, x.W, "dgrad") if F == 4 else 0), None, dx.p,
+        if plan.dgrad != "direct":   # backward-data of a stride-1 3x3 conv is one, too
+            F = int(plan.dgrad[1])
+            wino_conv(dout.p, dout.ld, x.B, x.H, x.W, self.O, self.I, wino_weight_cached(self.w, True, F, plan.dgrad_layout), None, dx.p,
                       dx.ld, acc_dx, F=F, role="dgrad", want_v=False)
             return
         wt = relayout_cached(self.w, (k, k, self.O, self.I), self.O, self.I, k, k, 1)
@@ -735,6 +746,10 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
         tape.append(("bn", name, x, y, stats, act, res, gathered))
         return y
 
+    def takes_lazy(name, B, H, W):   # may this 3x3 convolution's input be a LazyImg?
+        cout, cin = P[name + ".weight"].shape[:2]
+        return conv_plan(cin, cout, 3, 1, 1, B, H, W, training).takes_lazy
+
     def conv(name, x, k, s, p, bias=False, out=None):
         op = ConvOp(P[name + ".weight"], P[name + ".bias"] if bias else None, k, s, p)
         oh, ow = op.out_hw(x.H, x.W)
@@ -770,7 +785,7 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
     # half of the join buffer, the BatchNorm computes statistics only and the max-pool applies them to its windows: no apply pass over
     # the largest activation of the network (598 MB read + written at 16 x 304 x 480), no second copy of it.
     lazy_stem = (DEFER_BN and DEFER_UP_BN and DEFER_STEM_BN and not (training and syncbn.active())
-                 and ConvOp(P[pre + "dec_conv_stage1.weight"], None, 3, 1, 1).takes_lazy(B, Hp, Wp, training))
+                 and takes_lazy(pre + "dec_conv_stage1", B, Hp, Wp))
     c1 = Img(J[0], B, Hp, Wp, 0, 64) if lazy_stem else new_img(B, Hp, Wp, 64, dev)
     stem_g = _geom(B=B, IH=Hp + 6, IW=Wp + 8, OHl=Hp, OWl=Wp, OHa=Hp, OWa=Wp, IDX=4, TH=7, TW=2, KWF=2, Cin=16,
                    Cout=64, ld_in=4, ld_out=c1.ld)
@@ -794,7 +809,7 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
             has_ds = (q + "downsample.0.weight") in P
             z1 = conv(q + "conv1", x, 3, s, 1)
             defer = (DEFER_BN and not (training and syncbn.active())
-                     and ConvOp(P[q + "conv2.weight"], None, 3, 1, 1).takes_lazy(z1.B, z1.H, z1.W, training))
+                     and takes_lazy(q + "conv2", z1.B, z1.H, z1.W))
             y1 = bn(q + "bn1", z1, defer=defer)
             z = conv(q + "conv2", y1, 3, 1, 1)
             idt = bn(q + "downsample.1", conv(q + "downsample.0", x, 1, s, 0), act=0) if has_ds else x
@@ -821,7 +836,7 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
         # input transform normalises channels [cj, 2 cj) while it reads the buffer (the skip half is non-negative already: it passes
         # through relu(1 x + 0) unchanged) -- no apply pass over the up-sampled tensor (598 MB read + written at 16 x 304 x 480).
         lazy_up = (DEFER_BN and DEFER_UP_BN and not (training and syncbn.active())
-                   and ConvOp(P[cname + ".weight"], None, 3, 1, 1).takes_lazy(x.B, 2 * x.H, 2 * x.W, training))
+                   and takes_lazy(cname, x.B, 2 * x.H, 2 * x.W))
         if lazy_up:
             right = Img(J[lvl], x.B, 2 * x.H, 2 * x.W, cj, cj)
             up_raw = convT(tname + "0", x, out=right)

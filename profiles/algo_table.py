@@ -15,7 +15,7 @@ convolution is timed as
                staged by LDS-DMA; csrc/wino4c9.hip)
 and the dispatcher's choice for the roles is listed beside the fastest: `fwd` (a training forward pass; since round 6 the layers whose
 weight gradient runs in one kernel from x and dY keep no V, and their training forward is dispatched like `fwd_eval` --
-dense2d.forward_role), `fwd_eval` / `dgrad` (nothing is kept: the one-kernel form where it is eligible).  Writes
+dense2d.conv_plan), `fwd_eval` / `dgrad` (nothing is kept: the one-kernel form where it is eligible).  Writes
 profiles/r6_algo_table.md and .json (the CPU test
 tests/test_host_logic.py::test_dispatcher_follows_the_measured_algorithm_table asserts the dispatcher still makes these choices).
 Usage: python profiles/algo_table.py"""
@@ -67,19 +67,12 @@ class patched:
 
 
 def choice(cin, cout, B, H, W, role):
-    """The dispatcher's pick under the shipped thresholds (mopa_amd/dense2d.py: wino_tile, wino4_direct, wino4_fused)."""
-    F = dense2d.wino_tile(cin, cout, 3, 1, 1, B, H, W, "fwd" if role == "fwd_eval" else role)
-    if F == 0:
-        return "direct"
-    if F == 2:
-        return "F2"
-    lay = dense2d.wino4_layout(cin, cout, B, H, W, role)
-    return {3: "F4 one9", 2: "F4 one", 1: "F4 fused", 0: "F4"}[lay]
-
-
-def training_fwd_choice(cin, cout, B, H, W):
-    """The training forward pass: dispatched as "fwd_eval" where the weight gradient needs no V (dense2d.forward_role)."""
-    return choice(cin, cout, B, H, W, dense2d.forward_role(cin, cout, 3, 1, 1, B, H, W, True)[1])
+    """The dispatcher's pick under the shipped thresholds (mopa_amd/dense2d.py: conv_plan).  "fwd": a training forward pass -- it keeps V only
+    where the weight gradient is the two-operand form; "fwd_eval": a forward pass that keeps nothing; "dgrad": cin / cout are the
+    backward-data convolution's own."""
+    if role == "dgrad":
+        return dense2d.conv_plan(cout, cin, 3, 1, 1, B, H, W, True).dgrad
+    return dense2d.conv_plan(cin, cout, 3, 1, 1, B, H, W, role == "fwd").fwd
 
 
 def main():
@@ -122,7 +115,7 @@ def main():
                 if is_dgrad:   # (this row IS the backward-data convolution)
                     ch = {"fwd": "-", "fwd_eval": "-", "dgrad": choice(cin, cout, B, H, W, "dgrad")}
                 else:
-                    ch = {"fwd": training_fwd_choice(cin, cout, B, H, W), "fwd_eval": choice(cin, cout, B, H, W, "fwd_eval")}
+                    ch = {"fwd": choice(cin, cout, B, H, W, "fwd"), "fwd_eval": choice(cin, cout, B, H, W, "fwd_eval")}
                     ch["dgrad"] = choice(cout, cin, B, H, W, "dgrad") if cin == cout else "(next row)"
                 rows.append(dict(res=f"{H0}x{W0}", B=B, layer=name, cin=cin, cout=cout, H=H, W=W, us={k: round(v, 1) for k, v in t.items()}, best=best,
                                  chosen=ch, chosen_over_best={r: round(t[c] / t[best], 3) for r, c in ch.items() if c in t}))
