@@ -18,6 +18,13 @@
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Rows per block of mopa_colsum's partial sums (ops2d.hip); mopa_bn_act_bwd_groups_fused (rows.hip) forms the same partials.
+static inline int colsum_rows(int64_t num_rows) {
+  int64_t r = cdiv64(num_rows, 2048);
+  if (r < 32) r = 32;
+  if (r > 1024) r = 1024;
+  return (int)r;
+}
 
 // Grid size for grid-stride, HBM-bound kernels: enough blocks to fill 256 CUs x 8,
 // capped so tiny inputs do not launch empty blocks (guide: Guideline 11).

@@ -428,12 +428,6 @@ __global__ __launch_bounds__(256) void k_colsum_reduce(const float* __restrict__
   __syncthreads();
   if (threadIdx.x == 0) out[c] = (accumulate ? out[c] : 0.f) + (float)(((red[0] + red[1]) + red[2]) + red[3]);
 }
-static inline int colsum_rows(int64_t num_rows) {
-  int64_t r = cdiv64(num_rows, 2048);
-  if (r < 32) r = 32;
-  if (r > 1024) r = 1024;
-  return (int)r;
-}
 MOPA_API size_t mopa_colsum_workspace_bytes(int64_t num_rows, int32_t C) {
   return align_up((size_t)cdiv64(num_rows, colsum_rows(num_rows)) * C * sizeof(float), 256);
 }
@@ -447,6 +441,16 @@ MOPA_API int mopa_colsum(const float* x, int32_t ld, int64_t num_rows, int32_t C
   const int RL = 256 / (C >> 2);
   k_colsum_partial<<<nblk, 256, (size_t)RL * C * sizeof(float), st>>>(x, ld, (int)num_rows, C, rpb, (float*)ws);
   k_colsum_reduce<<<C, 256, 0, st>>>((const float*)ws, nblk, C, out, accumulate);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+// The second half of mopa_colsum alone, for a producer that has left the partial sums of mopa_colsum's partition itself
+// (mopa_bn_act_bwd_groups_fused, rows.hip).  partial MUST hold mopa_colsum_partial_blocks(num_rows) x C floats, block b's C sums at
+// partial + b * C: the count is derived from num_rows here and the slab's size cannot be checked.
+MOPA_API size_t mopa_colsum_partial_blocks(int64_t num_rows) { return (size_t)cdiv64(num_rows, colsum_rows(num_rows)); }
+MOPA_API int mopa_colsum_reduce(const float* partial, int64_t num_rows, int32_t C, float* out, int32_t accumulate, void* stream) {
+  if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || !partial || !out) return MOPA_ERR_ARG;
+  k_colsum_reduce<<<C, 256, 0, (hipStream_t)stream>>>(partial, (int)cdiv64(num_rows, colsum_rows(num_rows)), C, out, accumulate);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }

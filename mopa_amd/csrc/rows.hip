@@ -150,9 +150,17 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ p
 // y = act(x*scale + shift (+ res));  act: 0 = identity, 1 = leaky-ReLU(leak).
 // Thread = (row lane rl, channel quad cq): the per-channel constants live in registers and the thread walks rows
 // rl, rl + RL*grid, ... -- no per-element constant loads, no 64-bit division (the grid-stride form was TA-bound at 2.7 TB/s).
+// BITS (residual layers in training mode, act == 1, leak == 0): the ReLU decision of every element, pre-activation value > 0, is
+// also stored, one bit per element, for the backward pass to read in place of the whole saved output.  With leak == 0 the decision
+// equals `y > 0` of the stored output for every input, -0.0 and NaN included.  Layout: bits[row][C / 32] uint32; word w of a row holds
+// channels [32 w, 32 w + 32), channel c in bit (c & 31).  The thread (rl, cq) owns the nibble at bit 4 * (cq & 7) of word cq >> 3; the
+// eight threads that share a word are eight consecutive lanes on the same row (C % 32 == 0), OR their nibbles together with three
+// lane exchanges, and the first of them stores the word: no atomics.
+template <bool BITS>
 __global__ __launch_bounds__(256) void k_bn_relu_apply(const float* __restrict__ x, int ldx, float* __restrict__ y,
                                                         int ldy, const BnGroups grp, int C, const float* __restrict__ stats_all,
-                                                        float leak, const float* __restrict__ res, int ld_res, int act) {
+                                                        float leak, const float* __restrict__ res, int ld_res, int act,
+                                                        uint32_t* __restrict__ bits) {
   const int CQ = C >> 2, RL = 256 / CQ;
   const int cq = threadIdx.x % CQ, rl = threadIdx.x / CQ;
   if (rl >= RL) return;
@@ -168,6 +176,14 @@ __global__ __launch_bounds__(256) void k_bn_relu_apply(const float* __restrict__
     if (res) {
       const float4 rv = *reinterpret_cast<const float4*>(res + (int64_t)row * ld_res + cq * 4);
       o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
+    }
+    if (BITS) {
+      uint32_t m = (o.x > 0.f ? 1u : 0u) | (o.y > 0.f ? 2u : 0u) | (o.z > 0.f ? 4u : 0u) | (o.w > 0.f ? 8u : 0u);
+      m <<= (cq & 7) * 4;
+      m |= (uint32_t)__shfl_xor((int)m, 1);
+      m |= (uint32_t)__shfl_xor((int)m, 2);
+      m |= (uint32_t)__shfl_xor((int)m, 4);
+      if ((cq & 7) == 0) bits[(int64_t)row * (C >> 5) + (cq >> 3)] = m;
     }
     if (act) {
       o.x = o.x > 0.f ? o.x : o.x * leak; o.y = o.y > 0.f ? o.y : o.y * leak;
@@ -201,11 +217,11 @@ MOPA_API size_t mopa_bnrelu_rows_workspace_bytes(int32_t num_rows, int32_t C) {
 // tensor + one block per extra group.)
 // y == null: statistics, running statistics and stats only -- the consumer applies scale / shift / activation while it reads x
 // (mopa_wino4_input_bn: the BatchNorm between two convolutions of a ResNet block never materialises its output).
-MOPA_API int mopa_bn_act_fwd_groups(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t num_rows, int32_t C,
-                                    int32_t n_groups, int32_t split1, int32_t split2,
-                                    const float* gamma, const float* beta, float* running_mean, float* running_var,
-                                    float momentum, float eps, float leak, int32_t act, const float* res, int32_t ld_res,
-                                    int32_t training, float* stats, void* ws, size_t ws_bytes, void* stream) {
+static int bn_act_fwd_groups(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t num_rows, int32_t C,
+                             int32_t n_groups, int32_t split1, int32_t split2,
+                             const float* gamma, const float* beta, float* running_mean, float* running_var,
+                             float momentum, float eps, float leak, int32_t act, const float* res, int32_t ld_res,
+                             int32_t training, float* stats, uint32_t* bits, void* ws, size_t ws_bytes, void* stream) {
   if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ldx < C || (ldx & 3) || (y && (ldy < C || (ldy & 3)))) return MOPA_ERR_ARG;
   if (res && (ld_res < C || (ld_res & 3) || !y)) return MOPA_ERR_ARG;
   BnGroups grp;
@@ -222,10 +238,36 @@ MOPA_API int mopa_bn_act_fwd_groups(const float* x, int32_t ldx, float* y, int32
   if (y) {
     int maxrows = 0;
     for (int k = 0; k < grp.n; ++k) maxrows = grp.rows[k] > maxrows ? grp.rows[k] : maxrows;
-    k_bn_relu_apply<<<dim3(bn_apply_grid(maxrows, C), grp.n), 256, 0, st>>>(x, ldx, y, ldy, grp, C, stats, leak, res, ld_res, act);
+    if (bits)
+      k_bn_relu_apply<true><<<dim3(bn_apply_grid(maxrows, C), grp.n), 256, 0, st>>>(x, ldx, y, ldy, grp, C, stats, leak, res, ld_res, act,
+                                                                                    bits);
+    else
+      k_bn_relu_apply<false><<<dim3(bn_apply_grid(maxrows, C), grp.n), 256, 0, st>>>(x, ldx, y, ldy, grp, C, stats, leak, res, ld_res,
+                                                                                     act, nullptr);
   }
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
+}
+MOPA_API int mopa_bn_act_fwd_groups(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t num_rows, int32_t C,
+                                    int32_t n_groups, int32_t split1, int32_t split2,
+                                    const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                    float momentum, float eps, float leak, int32_t act, const float* res, int32_t ld_res,
+                                    int32_t training, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  return bn_act_fwd_groups(x, ldx, y, ldy, num_rows, C, n_groups, split1, split2, gamma, beta, running_mean, running_var, momentum, eps,
+                           leak, act, res, ld_res, training, stats, nullptr, ws, ws_bytes, stream);
+}
+// mopa_bn_act_fwd_groups that also leaves the activation bits of a residual layer (k_bn_relu_apply): want_bits = 1 needs bits[num_rows]
+// [C / 32], C % 32 == 0, a residual, act == 1, leak == 0 and training mode -- anything else is refused before the first launch.
+// want_bits = 0: mopa_bn_act_fwd_groups itself.
+MOPA_API int mopa_bn_act_fwd_groups_bits(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t num_rows, int32_t C,
+                                         int32_t n_groups, int32_t split1, int32_t split2,
+                                         const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                         float momentum, float eps, float leak, int32_t act, const float* res, int32_t ld_res,
+                                         int32_t training, float* stats, int32_t want_bits, uint32_t* bits, void* ws, size_t ws_bytes,
+                                         void* stream) {
+  if (want_bits && (!bits || C <= 0 || (C & 31) || leak != 0.f || !res || !y || act != 1 || !training)) return MOPA_ERR_ARG;
+  return bn_act_fwd_groups(x, ldx, y, ldy, num_rows, C, n_groups, split1, split2, gamma, beta, running_mean, running_var, momentum, eps,
+                           leak, act, res, ld_res, training, stats, want_bits ? bits : nullptr, ws, ws_bytes, stream);
 }
 MOPA_API int mopa_bn_act_fwd(const float* x, int32_t ldx, float* y, int32_t ldy, int32_t num_rows, int32_t C,
                              const float* gamma, const float* beta, float* running_mean, float* running_var,
@@ -254,11 +296,24 @@ __device__ __forceinline__ float bn_dz(float g, float xv, float sc, float sh, fl
   return yv > 0.f ? g : g * leak;
 }
 
+// The same decision from the forward pass's activation bit (k_bn_relu_apply<true>), again by value.
+__device__ __forceinline__ float bn_dz_bit(float g, float leak, int act, bool pos) {
+  if (!act) return g;
+  return pos ? g : g * leak;
+}
+// The nibble of thread cq (channels 4 cq .. 4 cq + 3 in bits 0 .. 3) from the row's mask words: the eight threads that share a word
+// load the same address.
+__device__ __forceinline__ uint32_t bn_mask_nibble(const uint32_t* __restrict__ bits, int64_t row, int C, int cq) {
+  return bits[row * (C >> 5) + (cq >> 3)] >> ((cq & 7) * 4);
+}
+
+// BITS: the activation mask is the forward pass's bit per element (`bits`, layout at k_bn_relu_apply) instead of the saved output.
+template <bool BITS>
 __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict__ dy, int ld_dy,
                                                          const float* __restrict__ x, int ldx, int C,
                                                          const float* __restrict__ stats, float leak,
                                                          const float* __restrict__ ymask, int ld_ym, int act, const BnGroups grp,
-                                                         float* __restrict__ partial) {
+                                                         float* __restrict__ partial, const uint32_t* __restrict__ bits) {
   extern __shared__ float lds[];
   const int gi = blockIdx.y;
   if ((int)blockIdx.x >= grp.nblk[gi]) return;
@@ -281,19 +336,23 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
     int row = rbeg + rl;
     for (; row + 3 * RL < rend; row += 4 * RL) {
       float4 xv[4], gv[4], yv[4];
+      uint32_t mw[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         xv[u] = *reinterpret_cast<const float4*>(x + (int64_t)(row + u * RL) * ldx + cq * 4);
         gv[u] = *reinterpret_cast<const float4*>(dy + (int64_t)(row + u * RL) * ld_dy + cq * 4);
         yv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ymask) yv[u] = *reinterpret_cast<const float4*>(ymask + (int64_t)(row + u * RL) * ld_ym + cq * 4);
+        mw[u] = 0u;
+        if (BITS) mw[u] = bn_mask_nibble(bits, row + u * RL, C, cq);
+        else if (ymask) yv[u] = *reinterpret_cast<const float4*>(ymask + (int64_t)(row + u * RL) * ld_ym + cq * 4);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w}, gs[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w}, ys[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
+          const float dz = BITS ? bn_dz_bit(gs[j], leak, act, (mw[u] >> j) & 1u)
+                                : bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
           s[j] += dz;
           ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
         }
@@ -303,11 +362,14 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
       const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)row * ldx + cq * 4);
       const float4 gv = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
       float4 yv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ymask) yv = *reinterpret_cast<const float4*>(ymask + (int64_t)row * ld_ym + cq * 4);
+      uint32_t mw = 0u;
+      if (BITS) mw = bn_mask_nibble(bits, row, C, cq);
+      else if (ymask) yv = *reinterpret_cast<const float4*>(ymask + (int64_t)row * ld_ym + cq * 4);
       const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
+        const float dz = BITS ? bn_dz_bit(gs[j], leak, act, (mw >> j) & 1u)
+                              : bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
         s[j] += dz;
         ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
       }
@@ -347,13 +409,61 @@ __global__ __launch_bounds__(256) void k_bn_bwd_finalize(const float* __restrict
 
 // training: dx = scale * (dz - mean(dz) - xhat * mean(dz*xhat));  eval: dx = scale * dz.   dx (+)= if acc_dx.
 // dres (optional) receives dz, the gradient of the residual input (+= if acc_dres).
-__global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ dy, int ld_dy, const float* __restrict__ x,
-                                                       int ldx, float* __restrict__ dx, int ld_dx, const BnGroups grp, int C,
-                                                       const float* __restrict__ stats, const float* __restrict__ coef,
-                                                       float leak, int training, int acc_dx, const float* __restrict__ ymask,
-                                                       int ld_ym, int act, float* __restrict__ dres, int ld_dres, int acc_dres) {
+struct BnApplyArgs {
+  const float* dy; int ld_dy;
+  const float* x; int ldx;
+  float* dx; int ld_dx;
+  const float* ymask; int ld_ym;
+  const uint32_t* bits;
+  float* dres; int ld_dres;
+  float leak; int training, acc_dx, act, acc_dres, C;
+};
+// One row of the apply pass for thread (., cq); o[0..3] = the four dx values as they were stored.
+template <bool BITS>
+__device__ __forceinline__ void bn_bwd_apply_row(const BnApplyArgs& a, int row, int cq, const float (&sc)[4], const float (&sh)[4],
+                                                 const float (&mean)[4], const float (&inv)[4], const float (&c0)[4],
+                                                 const float (&c1)[4], float (&o)[4]) {
+  const float4 xv = *reinterpret_cast<const float4*>(a.x + (int64_t)row * a.ldx + cq * 4);
+  const float4 gv = *reinterpret_cast<const float4*>(a.dy + (int64_t)row * a.ld_dy + cq * 4);
+  float4 yv = make_float4(0.f, 0.f, 0.f, 0.f);
+  uint32_t mw = 0u;
+  if (BITS) mw = bn_mask_nibble(a.bits, row, a.C, cq);
+  else if (a.ymask) yv = *reinterpret_cast<const float4*>(a.ymask + (int64_t)row * a.ld_ym + cq * 4);
+  const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
+  float dzv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float dz = BITS ? bn_dz_bit(gs[j], a.leak, a.act, (mw >> j) & 1u)
+                          : bn_dz(gs[j], xs[j], sc[j], sh[j], a.leak, a.act, a.ymask != nullptr, ys[j]);
+    dzv[j] = dz;
+    if (a.training) {
+      const float xhat = (xs[j] - mean[j]) * inv[j];
+      o[j] = sc[j] * (dz - c0[j] - xhat * c1[j]);
+    } else {
+      o[j] = sc[j] * dz;
+    }
+  }
+  float4* dp = reinterpret_cast<float4*>(a.dx + (int64_t)row * a.ld_dx + cq * 4);
+  if (a.acc_dx) {
+    const float4 p = *dp;
+    o[0] += p.x; o[1] += p.y; o[2] += p.z; o[3] += p.w;
+  }
+  *dp = make_float4(o[0], o[1], o[2], o[3]);
+  if (a.dres) {
+    float4* rp = reinterpret_cast<float4*>(a.dres + (int64_t)row * a.ld_dres + cq * 4);
+    if (a.acc_dres) {
+      const float4 p = *rp;
+      dzv[0] += p.x; dzv[1] += p.y; dzv[2] += p.z; dzv[3] += p.w;
+    }
+    *rp = make_float4(dzv[0], dzv[1], dzv[2], dzv[3]);
+  }
+}
+
+template <bool BITS>
+__global__ __launch_bounds__(256) void k_bn_bwd_apply(const BnApplyArgs a, const BnGroups grp, const float* __restrict__ stats,
+                                                       const float* __restrict__ coef) {
   // thread = (row lane, channel quad), constants in registers (see k_bn_relu_apply)
-  const int CQ = C >> 2, RL = 256 / CQ;
+  const int C = a.C, CQ = C >> 2, RL = 256 / CQ;
   const int cq = threadIdx.x % CQ, rl = threadIdx.x / CQ;
   if (rl >= RL) return;
   const int gi = blockIdx.y;
@@ -368,37 +478,56 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
   }
   const int A = grp.row0[gi] + grp.rows[gi];
   for (int row = grp.row0[gi] + blockIdx.x * RL + rl; row < A; row += gridDim.x * RL) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)row * ldx + cq * 4);
-    const float4 gv = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
-    float4 yv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ymask) yv = *reinterpret_cast<const float4*>(ymask + (int64_t)row * ld_ym + cq * 4);
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
-    float o[4], dzv[4];
+    float o[4];
+    bn_bwd_apply_row<BITS>(a, row, cq, sc, sh, mean, inv, c0, c1, o);
+  }
+}
+
+// The apply pass that also leaves the column sums of the dx it writes, as the partial sums mopa_colsum (ops2d.hip) would form from
+// that dx, bit for bit: the bias gradient of the convolution in front of this BatchNorm is sum_rows dx, and k_colsum_partial would
+// read the whole tensor again for it.  So this kernel takes k_colsum_partial's partition of the WHOLE tensor and its order of
+// additions: block b owns rows [b rpb, (b + 1) rpb) with rpb = colsum_rows(num_rows), thread (rl, cq) walks row = rbeg + rl, += RL
+// and adds its four stored values to s[0..3] in that order, the same LDS pass adds the RL row lanes.  (The stored value goes through
+// an empty asm statement first: the sum must add the rounded product, not contract with the multiplication that formed it.)
+// BatchNorm groups are row ranges with constants of their own: a block whose rows cross a group boundary re-loads scale, shift,
+// mean, invstd and the two coefficients at the boundary row and goes on with the same row walk.
+template <bool BITS>
+__global__ __launch_bounds__(256) void k_bn_bwd_apply_colsum(const BnApplyArgs a, const BnGroups grp, const float* __restrict__ stats_all,
+                                                              const float* __restrict__ coef_all, int A, int rpb,
+                                                              float* __restrict__ partial) {
+  extern __shared__ float lds[];  // [RL][C]
+  const int C = a.C, CQ = C >> 2, RL = 256 / CQ;
+  const int cq = threadIdx.x % CQ, rl = threadIdx.x / CQ;
+  const int rbeg = blockIdx.x * rpb, rend = min(A, rbeg + rpb);
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  if (rl < RL) {
+    int row = rbeg + rl;
+    for (int gi = 0; gi < grp.n; ++gi) {
+      const int gend = min(rend, grp.row0[gi] + grp.rows[gi]);
+      if (row >= gend) continue;
+      const float* __restrict__ stats = stats_all + (int64_t)gi * 4 * C;
+      const float* __restrict__ coef = coef_all + (int64_t)gi * 2 * C;
+      float sc[4], sh[4], mean[4], inv[4], c0[4], c1[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
-      dzv[j] = dz;
-      if (training) {
-        const float xhat = (xs[j] - mean[j]) * inv[j];
-        o[j] = sc[j] * (dz - c0[j] - xhat * c1[j]);
-      } else {
-        o[j] = sc[j] * dz;
+      for (int j = 0; j < 4; ++j) {
+        const int c = cq * 4 + j;
+        sc[j] = stats[c]; sh[j] = stats[C + c]; mean[j] = stats[2 * C + c]; inv[j] = stats[3 * C + c];
+        c0[j] = coef[c]; c1[j] = coef[C + c];
+      }
+      for (; row < gend; row += RL) {
+        float o[4];
+        bn_bwd_apply_row<BITS>(a, row, cq, sc, sh, mean, inv, c0, c1, o);
+        asm volatile("" : "+v"(o[0]), "+v"(o[1]), "+v"(o[2]), "+v"(o[3]));
+        s[0] += o[0]; s[1] += o[1]; s[2] += o[2]; s[3] += o[3];
       }
     }
-    float4* dp = reinterpret_cast<float4*>(dx + (int64_t)row * ld_dx + cq * 4);
-    if (acc_dx) {
-      const float4 p = *dp;
-      o[0] += p.x; o[1] += p.y; o[2] += p.z; o[3] += p.w;
-    }
-    *dp = make_float4(o[0], o[1], o[2], o[3]);
-    if (dres) {
-      float4* rp = reinterpret_cast<float4*>(dres + (int64_t)row * ld_dres + cq * 4);
-      if (acc_dres) {
-        const float4 p = *rp;
-        dzv[0] += p.x; dzv[1] += p.y; dzv[2] += p.z; dzv[3] += p.w;
-      }
-      *rp = make_float4(dzv[0], dzv[1], dzv[2], dzv[3]);
-    }
+    for (int j = 0; j < 4; ++j) lds[rl * C + cq * 4 + j] = s[j];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float t = 0.f;
+    for (int k = 0; k < RL; ++k) t += lds[k * C + c];
+    partial[(int64_t)blockIdx.x * C + c] = t;
   }
 }
 
@@ -409,14 +538,18 @@ MOPA_API size_t mopa_bnrelu_rows_bwd_workspace_bytes(int32_t num_rows, int32_t C
 // General backward of mopa_bn_act_fwd.  ymask: the forward output y (required when a residual was added; optional
 // otherwise).  dres: gradient of the residual input (optional).
 // The grouped form: stats = the forward's [n_groups][4][C]; the groups' parameter gradients add up in group order.
-MOPA_API int mopa_bn_act_bwd_groups(const float* dy, int32_t ld_dy, const float* x, int32_t ldx, float* dx, int32_t ld_dx,
-                                    int32_t num_rows, int32_t C, int32_t n_groups, int32_t split1, int32_t split2, const float* stats,
-                                    float leak, int32_t act, const float* ymask, int32_t ld_ym, float* dres, int32_t ld_dres,
-                                    int32_t accumulate_dres, int32_t training, float* dgamma, float* dbeta,
-                                    int32_t accumulate_param_grads, int32_t accumulate_dx, void* ws, size_t ws_bytes, void* stream) {
+// bits (in place of ymask): the activation bits of mopa_bn_act_fwd_groups_bits.  colsum_partial: the apply pass runs in mopa_colsum's
+// partition and leaves its partial sums of dx there (k_bn_bwd_apply_colsum).
+static int bn_act_bwd_groups(const float* dy, int32_t ld_dy, const float* x, int32_t ldx, float* dx, int32_t ld_dx,
+                             int32_t num_rows, int32_t C, int32_t n_groups, int32_t split1, int32_t split2, const float* stats,
+                             float leak, int32_t act, const float* ymask, int32_t ld_ym, const uint32_t* bits, float* dres,
+                             int32_t ld_dres, int32_t accumulate_dres, int32_t training, float* dgamma, float* dbeta,
+                             int32_t accumulate_param_grads, int32_t accumulate_dx, float* colsum_partial, void* ws, size_t ws_bytes,
+                             void* stream) {
   if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ldx < C || ld_dy < C || ld_dx < C || ((ldx | ld_dy | ld_dx) & 3))
     return MOPA_ERR_ARG;
   if ((ymask && (ld_ym < C || (ld_ym & 3))) || (dres && (ld_dres < C || (ld_dres & 3)))) return MOPA_ERR_ARG;
+  if (bits && ((C & 31) || leak != 0.f)) return MOPA_ERR_ARG;
   if (ws_bytes < mopa_bnrelu_rows_bwd_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
   BnGroups grp;
   if (!bn_make_groups(&grp, num_rows, n_groups, split1, split2)) return MOPA_ERR_ARG;
@@ -427,16 +560,61 @@ MOPA_API int mopa_bn_act_bwd_groups(const float* dy, int32_t ld_dy, const float*
   float* partial = (float*)ws;
   float* coef = (float*)((char*)ws + mopa_bnrelu_rows_workspace_bytes(num_rows, C));
   const int RL = 256 / (C >> 2);
-  k_bn_bwd_partial<<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(dy, ld_dy, x, ldx, C, stats, leak, ymask,
-                                                                                               ld_ym, act, grp, partial);
+  const dim3 pgrid(grp.nblk_max, grp.n);
+  const size_t plds = (size_t)2 * RL * C * sizeof(float);
+  if (bits)
+    k_bn_bwd_partial<true><<<pgrid, 256, plds, st>>>(dy, ld_dy, x, ldx, C, stats, leak, nullptr, 0, act, grp, partial, bits);
+  else
+    k_bn_bwd_partial<false><<<pgrid, 256, plds, st>>>(dy, ld_dy, x, ldx, C, stats, leak, ymask, ld_ym, act, grp, partial, nullptr);
   k_bn_bwd_finalize<<<C, 256, 0, st>>>(partial, grp, C, dgamma, dbeta, accumulate_param_grads, coef);
-  int maxrows = 0;
-  for (int k = 0; k < grp.n; ++k) maxrows = grp.rows[k] > maxrows ? grp.rows[k] : maxrows;
-  k_bn_bwd_apply<<<dim3(bn_apply_grid(maxrows, C), grp.n), 256, 0, st>>>(
-      dy, ld_dy, x, ldx, dx, ld_dx, grp, C, stats, coef, leak, training, accumulate_dx, ymask, ld_ym, act, dres,
-      ld_dres, accumulate_dres);
+  const BnApplyArgs aa = {dy, ld_dy, x, ldx, dx, ld_dx, bits ? nullptr : ymask, ld_ym, bits, dres, ld_dres,
+                          leak, training, accumulate_dx, act, accumulate_dres, C};
+  if (colsum_partial) {
+    const int rpb = colsum_rows(num_rows);
+    const int nblk = (int)cdiv64(num_rows, rpb);
+    const size_t alds = (size_t)RL * C * sizeof(float);
+    if (bits) k_bn_bwd_apply_colsum<true><<<nblk, 256, alds, st>>>(aa, grp, stats, coef, num_rows, rpb, colsum_partial);
+    else k_bn_bwd_apply_colsum<false><<<nblk, 256, alds, st>>>(aa, grp, stats, coef, num_rows, rpb, colsum_partial);
+  } else {
+    int maxrows = 0;
+    for (int k = 0; k < grp.n; ++k) maxrows = grp.rows[k] > maxrows ? grp.rows[k] : maxrows;
+    const dim3 agrid(bn_apply_grid(maxrows, C), grp.n);
+    if (bits) k_bn_bwd_apply<true><<<agrid, 256, 0, st>>>(aa, grp, stats, coef);
+    else k_bn_bwd_apply<false><<<agrid, 256, 0, st>>>(aa, grp, stats, coef);
+  }
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
+}
+MOPA_API int mopa_bn_act_bwd_groups(const float* dy, int32_t ld_dy, const float* x, int32_t ldx, float* dx, int32_t ld_dx,
+                                    int32_t num_rows, int32_t C, int32_t n_groups, int32_t split1, int32_t split2, const float* stats,
+                                    float leak, int32_t act, const float* ymask, int32_t ld_ym, float* dres, int32_t ld_dres,
+                                    int32_t accumulate_dres, int32_t training, float* dgamma, float* dbeta,
+                                    int32_t accumulate_param_grads, int32_t accumulate_dx, void* ws, size_t ws_bytes, void* stream) {
+  return bn_act_bwd_groups(dy, ld_dy, x, ldx, dx, ld_dx, num_rows, C, n_groups, split1, split2, stats, leak, act, ymask, ld_ym, nullptr,
+                           dres, ld_dres, accumulate_dres, training, dgamma, dbeta, accumulate_param_grads, accumulate_dx, nullptr, ws,
+                           ws_bytes, stream);
+}
+// mopa_bn_act_bwd_groups with the two savings of the 2D backbone's backward pass, each optional:
+//   use_bits = 1        the activation mask of a residual layer comes from `bits` (mopa_bn_act_fwd_groups_bits: one bit per element,
+//                       C % 32 == 0, leak == 0) instead of the saved output; use_bits = 0: recomputed from x, as with ymask == null;
+//   colsum_partial      (or null) receives mopa_colsum_partial_blocks(num_rows) x C partial column sums of the dx this call writes:
+//                       mopa_colsum_reduce on them gives what mopa_colsum(dx) gives, bit for bit, without reading dx again.
+// Without bits a residual gradient is refused (dres with act != 0: the mask of relu(bn(x) + res) is not a function of x).
+// dx, dres, dgamma and dbeta are those of mopa_bn_act_bwd_groups, bit for bit.
+MOPA_API size_t mopa_bn_act_bwd_groups_fused_workspace_bytes(int32_t num_rows, int32_t C) {
+  return mopa_bnrelu_rows_bwd_workspace_bytes(num_rows, C);
+}
+MOPA_API int mopa_bn_act_bwd_groups_fused(const float* dy, int32_t ld_dy, const float* x, int32_t ldx, float* dx, int32_t ld_dx,
+                                          int32_t num_rows, int32_t C, int32_t n_groups, int32_t split1, int32_t split2,
+                                          const float* stats, float leak, int32_t act, int32_t use_bits, const uint32_t* bits,
+                                          float* dres, int32_t ld_dres, int32_t accumulate_dres, int32_t training, float* dgamma,
+                                          float* dbeta, int32_t accumulate_param_grads, int32_t accumulate_dx, float* colsum_partial,
+                                          void* ws, size_t ws_bytes, void* stream) {
+  if (use_bits && (!bits || C <= 0 || (C & 31) || leak != 0.f)) return MOPA_ERR_ARG;
+  if (!use_bits && dres && act) return MOPA_ERR_ARG;   // a residual layer's mask cannot be recomputed from x: bits, or mopa_bn_act_bwd_groups
+  return bn_act_bwd_groups(dy, ld_dy, x, ldx, dx, ld_dx, num_rows, C, n_groups, split1, split2, stats, leak, act, nullptr, 0,
+                           use_bits ? bits : nullptr, dres, ld_dres, accumulate_dres, training, dgamma, dbeta, accumulate_param_grads,
+                           accumulate_dx, colsum_partial, ws, ws_bytes, stream);
 }
 // The reduction half of mopa_bn_act_bwd_groups alone: parameter gradients and coef_out[n_groups][2][C] = (mean(dz), mean(dz * xhat)) per
 // group -- for a consumer that applies dx = scale * (dz - coef0 - xhat * coef1) while it reads (dy, x) itself (mopa_stem_bwd_weight_bn:
@@ -454,8 +632,8 @@ MOPA_API int mopa_bn_bwd_sums_groups(const float* dy, int32_t ld_dy, const float
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
   const int RL = 256 / (C >> 2);
-  k_bn_bwd_partial<<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(dy, ld_dy, x, ldx, C, stats, leak, ymask,
-                                                                                               ld_ym, act, grp, partial);
+  k_bn_bwd_partial<false><<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(
+      dy, ld_dy, x, ldx, C, stats, leak, ymask, ld_ym, act, grp, partial, nullptr);
   k_bn_bwd_finalize<<<C, 256, 0, st>>>(partial, grp, C, dgamma, dbeta, accumulate_param_grads, coef_out);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
@@ -568,7 +746,7 @@ MOPA_API int mopa_bn_act_fwd_sync(const float* x, int32_t ldx, float* y, int32_t
   if (num_rows > 0) {
     BnGroups one;
     bn_make_groups(&one, num_rows, 1, 0, 0);
-    k_bn_relu_apply<<<bn_apply_grid(num_rows, C), 256, 0, st>>>(x, ldx, y, ldy, one, C, stats, leak, res, ld_res, act);
+    k_bn_relu_apply<false><<<bn_apply_grid(num_rows, C), 256, 0, st>>>(x, ldx, y, ldy, one, C, stats, leak, res, ld_res, act, nullptr);
   }
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
@@ -607,7 +785,8 @@ MOPA_API int mopa_bn_sync_bwd_sums(const float* dy, int32_t ld_dy, const float* 
   float* partial = (float*)ws;
   BnGroups one;
   bn_make_groups(&one, num_rows, 1, 0, 0);
-  k_bn_bwd_partial<<<nblk, 256, (size_t)2 * RL * C * sizeof(float), st>>>(dy, ld_dy, x, ldx, C, stats, leak, ymask, ld_ym, act, one, partial);
+  k_bn_bwd_partial<false><<<nblk, 256, (size_t)2 * RL * C * sizeof(float), st>>>(dy, ld_dy, x, ldx, C, stats, leak, ymask, ld_ym, act, one,
+                                                                                 partial, nullptr);
   k_bn_bwd_local_sums<<<C, 256, 0, st>>>(partial, nblk, C, dgamma, dbeta, accumulate_param_grads, sums);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
@@ -627,8 +806,8 @@ MOPA_API int mopa_bn_act_bwd_sync(const float* dy, int32_t ld_dy, const float* x
   k_bn_bwd_coef_sync<<<(2 * C + 255) / 256, 256, 0, st>>>(sums_global, gathered, world, C, coef_ws);
   BnGroups one;
   bn_make_groups(&one, num_rows, 1, 0, 0);
-  k_bn_bwd_apply<<<bn_apply_grid(num_rows, C), 256, 0, st>>>(dy, ld_dy, x, ldx, dx, ld_dx, one, C, stats, coef_ws, leak, 1,
-                                                             accumulate_dx, ymask, ld_ym, act, dres, ld_dres, accumulate_dres);
+  const BnApplyArgs aa = {dy, ld_dy, x, ldx, dx, ld_dx, ymask, ld_ym, nullptr, dres, ld_dres, leak, 1, accumulate_dx, act, accumulate_dres, C};
+  k_bn_bwd_apply<false><<<bn_apply_grid(num_rows, C), 256, 0, st>>>(aa, one, stats, coef_ws);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }

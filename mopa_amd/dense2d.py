@@ -542,8 +542,9 @@ class ConvOp:
         igemm(x.p, wl, self.b, out.p, self._fwd_geom(x, out))
 
     def backward(self, x: Img, dout: Img, dx: Img | None, dw: torch.Tensor, db, acc_dx: bool, acc_params: bool = False, V=None,
-                 wgrad_side: bool = False):
-        """wgrad_side: the caller joins the weight-gradient stream itself (join_wgrad_stream) after the whole backward pass."""
+                 wgrad_side: bool = False, db_partial=None):
+        """wgrad_side: the caller joins the weight-gradient stream itself (join_wgrad_stream) after the whole backward pass.
+        db_partial: the partial column sums of dout that its producer left (bn_bwd_fused): the bias gradient is their reduction."""
         dev = self.w.device
         k, s, p = self.k, self.s, self.p
         plan = conv_plan(self.I, self.O, k, s, p, x.B, x.H, x.W, True)   # (decided afresh from the switches as they are now)
@@ -553,13 +554,13 @@ class ConvOp:
         # and dout only and nothing downstream of this layer waits for it: it runs on the weight-gradient stream, beside the
         # backward-data chain that the rest of the backward pass is waiting for (Net2DFunction.backward joins the stream).
         ws = wgrad_stream(dev) if wgrad_side else None
-        with _on(ws, dout.t):   # (dout is dropped by the caller before the join; x, V, dw, db outlive it)
+        with _on(ws, dout.t, db_partial):   # (dout is dropped by the caller before the join; x, V, dw, db outlive it)
             if plan.wgrad_F:
                 wino_wgrad(x, dout, self.I, self.O, dw, V, accumulate=acc_params, F=plan.wgrad_F, fused=plan.wgrad == "F4 one")
             else:
                 wgrad(x.p, dout.p, ptr(dw), self._fwd_geom(x, dout), dev, accumulate=acc_params, oihw=True)
             if db is not None:
-                colsum(dout, db, accumulate=acc_params)
+                colsum(dout, db, accumulate=acc_params, partial=db_partial)
         if dx is None:
             return
         if plan.dgrad != "direct":   # backward-data of a stride-1 3x3 conv is one, too
@@ -607,9 +608,9 @@ class ConvTOp:
             for kx in range(2):
                 igemm(x.p, wl, self.b, out.p, self._geom(x, out, ky, kx))
 
-    def backward(self, x: Img, dout: Img, dx: Img, dw, db, acc_params: bool = False, wgrad_side: bool = False):
+    def backward(self, x: Img, dout: Img, dx: Img, dw, db, acc_params: bool = False, wgrad_side: bool = False, db_partial=None):
         dev = self.w.device
-        with _on(wgrad_stream(dev) if wgrad_side else None, dout.t):   # see ConvOp.backward
+        with _on(wgrad_stream(dev) if wgrad_side else None, dout.t, db_partial):   # see ConvOp.backward
             dwl = torch.empty(2, 2, self.I, self.O, dtype=torch.float32, device=dev)
             for ky in range(2):
                 for kx in range(2):
@@ -617,14 +618,18 @@ class ConvTOp:
                     g[17], g[18] = 0, 0  # KH0/KW0: the per-class launch writes a single-tap slab
                     wgrad(x.p, dout.p, ptr(dwl, (ky * 2 + kx) * self.I * self.O), g, dev)
             relayout(dwl, dw, self.O, self.I, 2, 2, 2, inverse=True, accumulate=acc_params)
-            colsum(dout, db, accumulate=acc_params)
+            colsum(dout, db, accumulate=acc_params, partial=db_partial)
         wt = relayout_cached(self.w, (2, 2, self.O, self.I), self.O, self.I, 2, 2, 3)
         g = _geom(B=x.B, IH=dout.H, IW=dout.W, OHl=x.H, OWl=x.W, OHa=x.H, OWa=x.W, IS=2, TH=2, TW=2, KWF=2,
                   Cin=self.O, Cout=self.I, ld_in=dout.ld, ld_out=dx.ld)
         igemm(dout.p, wt, None, dx.p, g, False)
 
 
-def colsum(x: View, out: torch.Tensor, accumulate=False):
+def colsum(x: View, out: torch.Tensor, accumulate=False, partial=None):
+    """out (+)= the column sums of x.  partial: mopa_colsum's partial sums of x, left by the kernel that wrote x: only the reduction runs."""
+    if partial is not None:
+        call("mopa_colsum_reduce", ptr(partial), x.rows, x.C, ptr(out), int(accumulate), stream())
+        return
     wsb = query("mopa_colsum_workspace_bytes", x.rows, x.C)
     ws = workspace.get(wsb, out.device)
     call("mopa_colsum", x.p, x.ld, x.rows, x.C, ptr(out), int(accumulate), ptr(ws), ws.numel(), stream())
@@ -637,6 +642,12 @@ DEFER_STEM_BN = os.environ.get("MOPA_DEFER_STEM_BN", "1") != "0"   # ... and the
 # A/B switch: the stem BatchNorm's backward apply inside the stem's weight gradient (mopa_stem_bwd_weight_bn: dx is never written)
 # (the stem's weight gradient with the BatchNorm backward formed in its loader exists as an MFMA kernel only: off with MOPA_CONV2D_MFMA=0)
 STEM_BN_FUSED_BWD = os.environ.get("MOPA_STEM_BN_FUSED_BWD", "1") != "0" and os.environ.get("MOPA_CONV2D_MFMA", "1") != "0"
+# A/B switch: the residual BatchNorms (bn2 of every BasicBlock) leave one bit per element, pre-activation > 0, and their backward pass
+# reads that bit instead of the whole saved output (mopa_bn_act_fwd_groups_bits / mopa_bn_act_bwd_groups_fused)
+BN_MASK_BITS = os.environ.get("MOPA_BN_MASK_BITS", "1") != "0"
+# A/B switch: a BatchNorm behind a convolution with a bias forms the partial column sums of its dx in its apply pass; the convolution's
+# bias gradient is mopa_colsum_reduce on them instead of mopa_colsum over dx (7 of the 8 decoder biases)
+BN_COLSUM_FUSED = os.environ.get("MOPA_BN_COLSUM_FUSED", "1") != "0"
 
 
 def bn_fwd(x: View, y: View, P, name, act, res, training, stats):
@@ -652,13 +663,20 @@ def bn_fwd(x: View, y: View, P, name, act, res, training, stats):
          ws.numel(), stream())
 
 
-def bn_fwd_groups(x: View, y: View | None, P, name, act, res, training, stats, G):
+def bn_fwd_groups(x: View, y: View | None, P, name, act, res, training, stats, G, bits=None):
     """bn_fwd for G consecutive, equally sized row groups of one tensor in ONE set of launches (3 instead of 3 G): statistics, running
     updates (group 0 first) and the apply per group, bit-identical to G calls of bn_fwd on the row ranges.  stats: (G, 4, C).
-    y = None: no apply pass (the consumer applies stats while it reads x: LazyImg)."""
+    y = None: no apply pass (the consumer applies stats while it reads x: LazyImg).
+    bits: (rows, C / 32) int32 that receives the activation bits of a residual layer for bn_bwd_fused."""
     n = x.rows // G
     wsb = query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C)
     ws = workspace.get(wsb, x.t.device)
+    if bits is not None:
+        call("mopa_bn_act_fwd_groups_bits", x.p, x.ld, y.p, y.ld, x.rows, x.C, G, n, 2 * n,
+             ptr(P[name + ".weight"]), ptr(P[name + ".bias"]),
+             ptr(P[name + ".running_mean"]), ptr(P[name + ".running_var"]), BN_MOMENTUM, BN_EPS, 0.0, int(act),
+             res.p, res.ld, int(training), ptr(stats), 1, ptr(bits), ptr(ws), ws.numel(), stream())
+        return
     call("mopa_bn_act_fwd_groups", x.p, x.ld, y.p if y is not None else None, y.ld if y is not None else 0, x.rows, x.C, G, n, 2 * n,
          ptr(P[name + ".weight"]), ptr(P[name + ".bias"]),
          ptr(P[name + ".running_mean"]), ptr(P[name + ".running_var"]), BN_MOMENTUM, BN_EPS, 0.0, int(act),
@@ -674,6 +692,22 @@ def bn_bwd_groups(dy: View, x: View, dx: View, stats, act, ymask, dres, acc_dres
          ymask.p if ymask is not None else None, ymask.ld if ymask is not None else 0,
          dres.p if dres is not None else None, dres.ld if dres is not None else 0, int(acc_dres), int(training),
          ptr(dgamma), ptr(dbeta), int(acc_params), 0, ptr(ws), ws.numel(), stream())
+
+
+def bn_bwd_fused(dy: View, x: View, dx: View, stats, act, bits, dres, acc_dres, training, dgamma, dbeta, G, acc_params=False,
+                 want_colsum=False):
+    """bn_bwd_groups with the activation mask from `bits` (bn_fwd_groups; None: recomputed from x) and, want_colsum, -> mopa_colsum's
+    partial sums of the dx it writes, a tensor of their own (the shared workspace is re-used by the kernels that follow)."""
+    n = x.rows // G
+    wsb = query("mopa_bn_act_bwd_groups_fused_workspace_bytes", x.rows, x.C)
+    ws = workspace.get(wsb, x.t.device)
+    partial = None
+    if want_colsum:
+        partial = torch.empty(query("mopa_colsum_partial_blocks", x.rows) * x.C, dtype=torch.float32, device=x.t.device)
+    call("mopa_bn_act_bwd_groups_fused", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act),
+         int(bits is not None), ptr(bits), dres.p if dres is not None else None, dres.ld if dres is not None else 0, int(acc_dres),
+         int(training), ptr(dgamma), ptr(dbeta), int(acc_params), 0, ptr(partial), ptr(ws), ws.numel(), stream())
+    return partial
 
 
 def bn_bwd(dy: View, x: View, dx: View, stats, act, ymask, dres, acc_dres, training, dgamma, dbeta, acc_dx=False,
@@ -732,18 +766,21 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
             y = LazyImg(x, stats, G)
             if training:
                 nbt.append(P[name + ".num_batches_tracked"])
-            tape.append(("bn", name, x, y, stats, act, None, [None] * G))
+            tape.append(("bn", name, x, y, stats, act, None, [None] * G, None))
             return y
         y = out if out is not None else new_img(x.B, x.H, x.W, x.C, dev)
-        if G > 1 and not (training and syncbn.active()):
-            bn_fwd_groups(x, y, P, name, act, res, training, stats, G)     # one set of launches for all groups
+        bits = None
+        if BN_MASK_BITS and keep_tape and training and res is not None and act == 1 and x.C % 32 == 0 and not syncbn.active():
+            bits = torch.empty(x.rows, x.C // 32, dtype=torch.int32, device=dev)   # the ReLU mask for the backward pass, 1 bit per element
+        if bits is not None or (G > 1 and not (training and syncbn.active())):
+            bn_fwd_groups(x, y, P, name, act, res, training, stats, G, bits)     # one set of launches for all groups
             gathered = [None] * G
         else:
             gathered = [bn_fwd(_group(x, g, G), _group(y, g, G), P, name, act, None if res is None else _group(res, g, G), training,
                                stats[g]) for g in range(G)]
         if training:
             nbt.append(P[name + ".num_batches_tracked"])
-        tape.append(("bn", name, x, y, stats, act, res, gathered))
+        tape.append(("bn", name, x, y, stats, act, res, gathered, bits))
         return y
 
     def takes_lazy(name, B, H, W):   # may this 3x3 convolution's input be a LazyImg?
@@ -892,10 +929,13 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
 
     gmap[key(feat)] = dfeat
     dJ = {}  # gradient buffers of the join tensors (full width)
+    # outputs of the convolutions with a bias: a BatchNorm that reads one leaves the partial column sums of its dx for the bias gradient
+    biased = {key(r[4]) for r in tape if r[0] in ("conv", "convT") and r[2].b is not None} if BN_COLSUM_FUSED else set()
+    db_partials = {}
     for rec in reversed(tape):
         kind = rec[0]
         if kind == "bn":
-            _, name, x, y, stats, act, res, gathered = rec
+            _, name, x, y, stats, act, res, gathered, bits = rec
             dy = gmap.pop(key(y))
             dres = None
             acc_dres = False
@@ -920,7 +960,15 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
                 continue
             dx = like(x)
             gmap[key(x)] = dx
-            if G > 1 and all(gt is None for gt in gathered):
+            local = all(gt is None for gt in gathered)   # (not synchronised)
+            # (the fused entry point has no ymask: a residual layer without bits keeps the path that reads the saved output)
+            fusable = local and (res is None or bits is not None)
+            want_colsum = fusable and key(x) in biased
+            if fusable and (bits is not None or want_colsum):
+                part = bn_bwd_fused(dy, x, dx, stats, act, bits, dres, acc_dres, training, dg, db, G, acc_params=pacc, want_colsum=want_colsum)
+                if want_colsum:
+                    db_partials[key(x)] = part
+            elif G > 1 and local:
                 bn_bwd_groups(dy, x, dx, stats, act, y if res is not None else None, dres, acc_dres, training, dg, db, G, acc_params=pacc)
             else:
                 for g in range(G):
@@ -935,14 +983,15 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
             dx = gmap[k] if acc else like(x)
             gmap[k] = dx
             pg, pacc = sink.take(*([name + ".weight"] + ([name + ".bias"] if op.b is not None else [])))
-            op.backward(x, dout, dx, pg[0], pg[1] if op.b is not None else None, acc, acc_params=pacc, V=V, wgrad_side=True)
+            op.backward(x, dout, dx, pg[0], pg[1] if op.b is not None else None, acc, acc_params=pacc, V=V, wgrad_side=True,
+                        db_partial=db_partials.pop(key(out), None))
         elif kind == "convT":
             _, name, op, x, out = rec
             dout = gmap.pop(key(out))
             dx = like(x)
             gmap[key(x)] = dx
             (dw, db), pacc = sink.take(name + ".weight", name + ".bias")
-            op.backward(x, dout, dx, dw, db, acc_params=pacc, wgrad_side=True)
+            op.backward(x, dout, dx, dw, db, acc_params=pacc, wgrad_side=True, db_partial=db_partials.pop(key(out), None))
         elif kind == "join":
             _, lvl, cj, lazy_up, lazy_left = rec
             lz = (1,) if lazy_up else ()   # (the join was consumed as a LazyImg: see key())
