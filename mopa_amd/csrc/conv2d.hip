@@ -982,6 +982,250 @@ MOPA_API int mopa_stem_bwd_weight_bn(const float* in, const float* dy, int32_t l
   return MOPA_OK;
 }
 
+// The stem's weight gradient from an image STRIP instead of an im2col tile.  On the dense stem geometry (stride 1, the zero-padded
+// NHWC4 image of mopa_img_to_nhwc4: stem_strip_geom) GEMM row (ty, 4-pixel tap tx, slot k16) of output pixel (oy, ox) is float
+// 4 * ox + 16 * tx + k16 of image row oy + ty, so filter row ty's 32 GEMM rows are 32 CONSECUTIVE floats of that row and the operand of
+// the neighbouring output pixel starts 4 floats further on.  A chunk is a run of up to SP output pixels of one output row, clipped to
+// the block's pixel range: the block stages 7 rows x (len + 7) pixels of the image (8 KB at SP = 64 against 57 KB of im2col, which
+// repeats every image pixel up to 56 times) and every lane reads its A operand straight from the strip, Ss[ty][4 * pixel + l32].
+// The chunk cursor (image, row, column, linear pixel) is block-uniform: no per-lane pixel loops, every load is `uniform base +
+// per-lane offset` and unconditional -- a slot past the chunk re-reads the chunk's first element and is zeroed when it is staged --
+// and the next chunk's loads are issued before the current chunk's MFMAs (one wait, in front of the staging stores behind them).
+// Same partition (wgrad_split), same slabs, same 32x32x2 MFMA as k_stem_wgrad_mfma, every accumulator takes its range's pixels in
+// ascending order: the MFMA is an fmaf chain in k order and a zeroed slot adds fmaf(0, 0, acc), so the slabs have that kernel's bits.
+#define SP 64
+#define SSLOTS 512   // float4 slots of one strip buffer (7 * (SP + 7) = 497 used)
+static_assert(7 * (SP + 7) <= SSLOTS && SP % 16 == 0, "strip staging: two float4 per thread");
+// One chunk's MFMAs of a wave with NT row tiles (rt0, rt0 + 2, ...): sp = the strip at (row rt0, this lane's float), bp = the staged
+// output gradient at (pixel lk, this lane's channel); pixel pair i is 8 floats / 2 rows further on.  The operands of pair i + 1 are
+// read from LDS before the MFMAs of pair i (the last pair reads itself again); np >= 1.
+template <int NT>
+__device__ __forceinline__ void stem_strip_mma(f32x16 (&acc)[4], const float* sp, const float* bp, int np) {
+  constexpr int SW = 4 * (SP + 7);
+  float b0 = bp[0], a0[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) a0[n] = sp[n * 2 * SW];
+#define STEM_STRIP_PAIR(I)                                                                                          \
+  {                                                                                                                 \
+    const int nx = min((I) + 1, np - 1);                                                                            \
+    const float b1 = bp[nx * 128];                                                                                  \
+    float a1[NT];                                                                                                   \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) a1[n] = sp[n * 2 * SW + nx * 8];                                 \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[n], b0, acc[n], 0, 0, 0); \
+    b0 = b1;                                                                                                        \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) a0[n] = a1[n];                                                   \
+  }
+  int i = 0;
+  for (; i + 4 <= np; i += 4) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) STEM_STRIP_PAIR(i + u)
+  }
+  for (; i < np; ++i) STEM_STRIP_PAIR(i)
+#undef STEM_STRIP_PAIR
+}
+template <bool BNB>
+__global__ __launch_bounds__(256, 2) void k_stem_wgrad_strip(const float* __restrict__ in, const float* __restrict__ dy,
+                                                              float* __restrict__ slabs, const ConvGeom g, int m_per_split,
+                                                              const StemBn bn) {
+  constexpr int SW = 4 * (SP + 7);   // floats per strip row
+  constexpr int NB = SP / 16;        // output-gradient float4 per thread and chunk
+  __shared__ __attribute__((aligned(16))) float Ss[2][SSLOTS * 4];
+  __shared__ __attribute__((aligned(16))) float Bs[2][SP][64];
+  __shared__ __attribute__((aligned(16))) float cst[BNB ? 3 : 1][6][BNB ? 64 : 4];   // as in k_stem_wgrad_mfma
+  const int t = threadIdx.x;
+  if (BNB) {
+    for (int i = t; i < bn.n_groups * 6 * 64; i += 256) {
+      const int gi = i / 384, k = (i - gi * 384) >> 6, c = i & 63;
+      cst[gi][k][c] = k < 4 ? bn.stats[(gi * 4 + k) * 64 + c] : bn.coef[(gi * 2 + (k - 4)) * 64 + c];
+    }
+  }
+  const int M = g.B * g.OHl * g.OWl, ohw = g.OHl * g.OWl;
+  const int mbeg = blockIdx.x * m_per_split, mend = min(M, mbeg + m_per_split);
+  const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // (the wave's row tiles are a scalar branch, not an exec mask)
+  const int wco = (wv & 1) * 32, rt0 = wv >> 1;
+  const int l32 = lane & 31, lk = lane >> 5;
+  const int ld_dy = BNB ? bn.ld_dy : g.ld_out;
+  f32x16 acc[4];
+#pragma unroll
+  for (int n = 0; n < 4; ++n)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
+  // staging: strip slot e = t + 256 j = (row e / (SP + 7), pixel column e % (SP + 7)); output gradient: pixel t / 16 + 16 j, quad t % 16
+  int scol[2], soff[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int e = t + 256 * j, r = e / (SP + 7);
+    scol[j] = e < 7 * (SP + 7) ? e - r * (SP + 7) : 2 * SP;   // (a slot past the strip is never inside a chunk)
+    soff[j] = (r * g.IW + scol[j]) * 4;
+  }
+  const int bpx = t >> 4, bq = t & 15;
+  float4 rs[2], rb[NB], rx[NB];
+  // the chunk cursor: block-uniform
+  int cm = mbeg, cb = __builtin_amdgcn_readfirstlane(cm / ohw), cy = __builtin_amdgcn_readfirstlane((cm - cb * ohw) / g.OWl);
+  int cx = cm - cb * ohw - cy * g.OWl;
+  int llen = 0, lgi = 0;   // length and BatchNorm group of the chunk in the registers
+  auto load_chunk = [&]() {
+    const int len = min(min(SP, g.OWl - cx), mend - cm);
+    const float* sbase = in + ((int64_t)(cb * g.IH + cy) * g.IW + cx) * 4;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) rs[j] = *reinterpret_cast<const float4*>(sbase + (scol[j] < len + 7 ? soff[j] : 0));
+    const float* dbase = dy + (int64_t)cm * ld_dy + bq * 4;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) rb[j] = *reinterpret_cast<const float4*>(dbase + (bpx + 16 * j < len ? (bpx + 16 * j) * ld_dy : 0));
+    if (BNB) {
+      const float* xbase = bn.xbn + (int64_t)cm * bn.ld_x + bq * 4;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) rx[j] = *reinterpret_cast<const float4*>(xbase + (bpx + 16 * j < len ? (bpx + 16 * j) * bn.ld_x : 0));
+      lgi = cb / bn.imgs_per_group;
+    }
+    llen = len;
+    cm += len;
+    cx += len;
+    if (cx == g.OWl) {
+      cx = 0;
+      if (++cy == g.OHl) { cy = 0; ++cb; }
+    }
+  };
+  auto store_chunk = [&](int buf) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const bool ok = scol[j] < llen + 7;
+      *reinterpret_cast<float4*>(&Ss[buf][(t + 256 * j) * 4]) =
+          make_float4(ok ? rs[j].x : 0.f, ok ? rs[j].y : 0.f, ok ? rs[j].z : 0.f, ok ? rs[j].w : 0.f);
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const bool ok = bpx + 16 * j < llen;
+      float o[4] = {rb[j].x, rb[j].y, rb[j].z, rb[j].w};
+      if (BNB) {
+        const float xs[4] = {rx[j].x, rx[j].y, rx[j].z, rx[j].w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int c = bq * 4 + q;
+          const float sc = cst[lgi][0][c], sh = cst[lgi][1][c], mean = cst[lgi][2][c], inv = cst[lgi][3][c], c0 = cst[lgi][4][c], c1 = cst[lgi][5][c];
+          const float gs = o[q];
+          const float yv = fmaf(xs[q], sc, sh);
+          const float dz = yv > 0.f ? gs : gs * 0.f;
+          if (bn.training) {
+            const float xhat = (xs[q] - mean) * inv;
+            o[q] = sc * (dz - c0 - xhat * c1);
+          } else {
+            o[q] = sc * dz;
+          }
+        }
+      }
+      *reinterpret_cast<float4*>(&Bs[buf][bpx + 16 * j][bq * 4]) = make_float4(ok ? o[0] : 0.f, ok ? o[1] : 0.f, ok ? o[2] : 0.f, ok ? o[3] : 0.f);
+    }
+  };
+  int buf = 0, len = 0;
+  if (BNB) __syncthreads();   // cst
+  if (mbeg < mend) {
+    load_chunk();
+    store_chunk(0);
+    len = llen;
+  }
+  __syncthreads();
+  while (len > 0) {
+    const bool more = cm < mend;
+    if (more) load_chunk();
+    const float* sp = &Ss[buf][rt0 * SW + 4 * lk + l32];
+    const float* bp = &Bs[buf][lk][wco + l32];
+    const int np = (len + 1) >> 1;   // pixel pairs (an odd chunk's last slot is zero)
+    if (rt0 == 0) stem_strip_mma<4>(acc, sp, bp, np);   // row tiles 0, 2, 4, 6
+    else stem_strip_mma<3>(acc, sp, bp, np);            // row tiles 1, 3, 5
+    if (more) {
+      store_chunk(buf ^ 1);
+      __syncthreads();
+      buf ^= 1;
+      len = llen;
+    } else {
+      len = 0;
+    }
+  }
+  float* dst = slabs + (int64_t)blockIdx.x * STEM_ROWS * 64 + wco + l32;
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int rt = rt0 + 2 * n;
+    if (rt < 7) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) dst[(int64_t)(rt * 32 + 8 * (e >> 2) + 4 * lk + (e & 3)) * 64] = acc[n][e];
+    }
+  }
+}
+// The geometry the strip kernel takes: the dense 7x7 stem on the padded NHWC4 image, output written where it is computed.
+static bool stem_strip_geom(const ConvGeom& g) {
+  return stem_wgrad_mfma(g) && g.IS == 1 && g.IY0 == 0 && g.IX0 == 0 && g.IDY == 1 && g.IDX == 4 && g.ld_in == 4 && g.OS == 1 &&
+         g.OOY == 0 && g.OOX == 0 && g.OHa == g.OHl && g.OWa == g.OWl && g.IH >= g.OHl + 6 && g.IW >= g.OWl + 7 && g.B > 0 && g.OHl > 0 &&
+         g.OWl > 0 && (int64_t)g.B * g.IH * g.IW < (1ll << 29);
+}
+// k_reduce_slabs2<16>'s sums of the stem's slabs (14,336 elements: reduce_ew's narrowest form) written through k_stem_relayout's
+// inverse map into torch's [64][3][7][7] gradient: reduction and relayout of the stem's weight gradient as one launch, same bits.
+__global__ __launch_bounds__(256) void k_reduce_slabs_stem(const float* __restrict__ slabs, int nsplit, float* __restrict__ dw, int accumulate) {
+  constexpr int EW = 16, NL = 256 / EW, n = STEM_ROWS * 64;
+  __shared__ float red[NL][EW + 1];
+  const int el = threadIdx.x % EW, cl = threadIdx.x / EW;
+  const int i = blockIdx.x * EW + el;
+  float s = 0.f;
+#pragma unroll 8
+  for (int c = cl; c < nsplit; c += NL) s += slabs[(int64_t)c * n + i];
+  red[cl][el] = s;
+  __syncthreads();
+  if (cl == 0) {
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) t += red[k][el];
+    const int o = i % 64;
+    int r = i / 64;
+    const int k16 = r % 16; r /= 16;
+    const int tx = r % 2, kh = r / 2;
+    const int kw = 4 * tx + k16 / 4, c = k16 % 4;
+    if (kw < 7 && c < 3) {
+      const int p = ((o * 3 + c) * 7 + kh) * 7 + kw;
+      dw[p] = (accumulate ? dw[p] : 0.f) + t;
+    }
+  }
+}
+static int stem_wgrad2_launch(const float* in, const float* dy, float* dweight, const int32_t* geom_host, int32_t flags, void* ws,
+                              size_t ws_bytes, void* stream, const StemBn* bn) {
+  ConvGeom g;
+  memcpy(&g, geom_host, sizeof(g));
+  const int accumulate = flags & 1, param = (flags >> 1) & 1;
+  if (!stem_strip_geom(g) || !in || !dy || !dweight || (flags & ~3)) return MOPA_ERR_ARG;
+  if (!bn && (g.ld_out < 64 || (g.ld_out & 3))) return MOPA_ERR_ARG;
+  static_assert(STEM_ROWS * 64 < 32 * 512, "k_reduce_slabs_stem is k_reduce_slabs2<16>");
+  if (ws_bytes < mopa_conv2d_wgrad_workspace_bytes(geom_host)) return MOPA_ERR_WORKSPACE;
+  int ns, mps;
+  wgrad_split(g, &ns, &mps);
+  hipStream_t st = (hipStream_t)stream;
+  float* slabs = (float*)ws;
+  if (bn) k_stem_wgrad_strip<true><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, *bn);
+  else k_stem_wgrad_strip<false><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, StemBn{});
+  const int n = STEM_ROWS * 64;
+  if (param) k_reduce_slabs_stem<<<n / 16, 256, 0, st>>>(slabs, ns, dweight, accumulate);
+  else reduce_slabs2_launch(slabs, ns, n, dweight, accumulate, 0, 14, 16, 64, st);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+// mopa_conv2d_bwd_weight of the stem through k_stem_wgrad_strip: same workspace, same slabs, same bits.  The dense stem geometry only
+// (stem_strip_geom; anything else is MOPA_ERR_ARG: mopa_conv2d_bwd_weight takes it).
+// flags: bit 0 = accumulate into dweight; bit 1 = dweight is torch's parameter gradient [64][3][7][7] (the ordered slab reduction writes
+// it through mopa_conv2d_stem_relayout's inverse map: that call's bits without the [7][2][16][64] tensor and its launch).
+MOPA_API int mopa_stem_bwd_weight2(const float* in, const float* dy, float* dweight, const int32_t* geom_host, int32_t flags, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  return stem_wgrad2_launch(in, dy, dweight, geom_host, flags, ws, ws_bytes, stream, nullptr);
+}
+// mopa_stem_bwd_weight_bn through k_stem_wgrad_strip; arguments as there, geometry and flags as mopa_stem_bwd_weight2.
+MOPA_API int mopa_stem_bwd_weight_bn2(const float* in, const float* dy, int32_t ld_dy, const float* xbn, int32_t ld_x, const float* stats,
+                                      const float* coef, int32_t n_groups, int32_t training, float* dweight, const int32_t* geom_host,
+                                      int32_t flags, void* ws, size_t ws_bytes, void* stream) {
+  ConvGeom g;
+  memcpy(&g, geom_host, sizeof(g));
+  if (n_groups < 1 || n_groups > 3 || g.B <= 0 || g.B % n_groups || ld_dy < 64 || ld_x < 64 || ((ld_dy | ld_x) & 3) || !xbn || !stats || !coef)
+    return MOPA_ERR_ARG;
+  const StemBn bn{xbn, stats, coef, ld_x, ld_dy, g.B / n_groups, n_groups, training};
+  return stem_wgrad2_launch(in, dy, dweight, geom_host, flags, ws, ws_bytes, stream, &bn);
+}
+
 // ----------------------------------------------------------------------------------------------
 // Weight gradient of a Winograd-eligible 3x3 convolution in the transform domain (2.25x fewer multiplies than the direct
 // form):  dU[p][ci][co] = sum_t V[p][t][ci] * dM[p][t][co]  -- 16 independent 1x1 weight gradients over the T tiles, run as

@@ -638,6 +638,142 @@ MOPA_API int mopa_bn_bwd_sums_groups(const float* dy, int32_t ld_dy, const float
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }
+// k_bn_bwd_partial (saved-output mask recomputed from x) over a dy that a 3x3 / stride 2 / padding 1 max-pool's backward still has to
+// add its share to: row (b, iy, ix) of dy is formed here -- the up to four pooling windows over the pixel in k_maxpool_bwd's order
+// (window row, then window column, from 0.f), then the value dy already holds when `accumulate` -- used for the sums and written back,
+// so the tensor gets k_maxpool_bwd's bits without that kernel's pass over it.  Same block partition, same row order per thread, same
+// LDS pass as k_bn_bwd_partial: same partial sums.  Loads are unconditional: a window that does not cover the pixel (or lies outside
+// the pooled map) re-reads the pixel's first window and its tap code is one no argmax byte takes.
+struct PoolBwdArgs { const float* dpool; int ld_dpool; const unsigned char* argmax; int H, W, OH, OW; };
+struct PoolRow { float4 g[4]; uchar4 w[4]; float4 q; int tap[4]; };
+__device__ __forceinline__ void pool_bwd_row_load(const PoolBwdArgs& p, const float* __restrict__ dy, int ld_dy, int C, int row, int cq,
+                                                  bool accumulate, PoolRow& o) {
+  const int ix = row % p.W, r = row / p.W;
+  const int iy = r % p.H, b = r / p.H;
+  const int by = iy >> 1, py = iy & 1, bx = ix >> 1, px = ix & 1;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const bool ok = a <= py && c <= px && by + a < p.OH && bx + c < p.OW;
+      const int64_t w = (int64_t)(b * p.OH + by + (ok ? a : 0)) * p.OW + bx + (ok ? c : 0);
+      o.tap[a * 2 + c] = ok ? (a == 0 ? 1 + py : 0) * 3 + (c == 0 ? 1 + px : 0) : 255;
+      o.w[a * 2 + c] = *reinterpret_cast<const uchar4*>(p.argmax + w * C + cq * 4);
+      o.g[a * 2 + c] = *reinterpret_cast<const float4*>(p.dpool + w * p.ld_dpool + cq * 4);
+    }
+  o.q = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (accumulate) o.q = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
+}
+__device__ __forceinline__ float4 pool_bwd_row_value(const PoolRow& o, bool accumulate) {
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    s[0] = o.w[k].x == o.tap[k] ? s[0] + o.g[k].x : s[0];
+    s[1] = o.w[k].y == o.tap[k] ? s[1] + o.g[k].y : s[1];
+    s[2] = o.w[k].z == o.tap[k] ? s[2] + o.g[k].z : s[2];
+    s[3] = o.w[k].w == o.tap[k] ? s[3] + o.g[k].w : s[3];
+  }
+  if (accumulate) { s[0] += o.q.x; s[1] += o.q.y; s[2] += o.q.z; s[3] += o.q.w; }
+  return make_float4(s[0], s[1], s[2], s[3]);
+}
+__global__ __launch_bounds__(256) void k_bn_bwd_partial_pool(const PoolBwdArgs pool, float* __restrict__ dy, int ld_dy, int accumulate_dy,
+                                                              const float* __restrict__ x, int ldx, int C,
+                                                              const float* __restrict__ stats, float leak, int act, const BnGroups grp,
+                                                              float* __restrict__ partial) {
+  extern __shared__ float lds[];
+  const int gi = blockIdx.y;
+  if ((int)blockIdx.x >= grp.nblk[gi]) return;
+  const int CQ = C >> 2;
+  const int RL = 256 / CQ;
+  const int cq = threadIdx.x % CQ, rl = threadIdx.x / CQ;
+  const int rpb = grp.rpb[gi];
+  const int rbeg = grp.row0[gi] + blockIdx.x * rpb, rend = min(grp.row0[gi] + grp.rows[gi], rbeg + rpb);
+  partial += (int64_t)grp.poff[gi] * 2 * C;
+  stats += (int64_t)gi * 4 * C;
+  float s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+  if (rl < RL) {
+    float sc[4], sh[4], mu[4], is[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      sc[j] = stats[cq * 4 + j]; sh[j] = stats[C + cq * 4 + j];
+      mu[j] = stats[2 * C + cq * 4 + j]; is[j] = stats[3 * C + cq * 4 + j];
+    }
+    // four rows of loads in flight per thread, summed in row order (k_bn_bwd_partial)
+    int row = rbeg + rl;
+    for (; row + 3 * RL < rend; row += 4 * RL) {
+      float4 xv[4];
+      PoolRow pr[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        xv[u] = *reinterpret_cast<const float4*>(x + (int64_t)(row + u * RL) * ldx + cq * 4);
+        pool_bwd_row_load(pool, dy, ld_dy, C, row + u * RL, cq, accumulate_dy != 0, pr[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float4 gv = pool_bwd_row_value(pr[u], accumulate_dy != 0);
+        *reinterpret_cast<float4*>(dy + (int64_t)(row + u * RL) * ld_dy + cq * 4) = gv;
+        const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, false, 0.f);
+          s[j] += dz;
+          ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
+        }
+      }
+    }
+    for (; row < rend; row += RL) {
+      const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)row * ldx + cq * 4);
+      PoolRow pr;
+      pool_bwd_row_load(pool, dy, ld_dy, C, row, cq, accumulate_dy != 0, pr);
+      const float4 gv = pool_bwd_row_value(pr, accumulate_dy != 0);
+      *reinterpret_cast<float4*>(dy + (int64_t)row * ld_dy + cq * 4) = gv;
+      const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, false, 0.f);
+        s[j] += dz;
+        ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      lds[(0 * RL + rl) * C + cq * 4 + j] = s[j];
+      lds[(1 * RL + rl) * C + cq * 4 + j] = ss[j];
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * C; i += 256) {
+    const int which = i / C, c = i - which * C;
+    float t = 0.f;
+    for (int k = 0; k < RL; ++k) t += lds[(which * RL + k) * C + c];
+    partial[(int64_t)blockIdx.x * 2 * C + i] = t;
+  }
+}
+// mopa_maxpool3x3s2_bwd(dpool, argmax -> dy, accumulate_dy) followed by mopa_bn_bwd_sums_groups(dy, x; no saved-output mask) over the
+// B * H * W rows of the pool's input, as the sums pass alone (k_bn_bwd_partial_pool + k_bn_bwd_finalize): dy is left as the pool's
+// backward leaves it, dgamma / dbeta / coef_out as the sums call leaves them.  The B images are n_groups equal consecutive groups.
+// Refuses what either of the two calls refuses.
+MOPA_API int mopa_bn_bwd_sums_groups_pool(const float* dpool, int32_t ld_dpool, const uint8_t* argmax, int32_t B, int32_t H, int32_t W,
+                                          float* dy, int32_t ld_dy, int32_t accumulate_dy, const float* x, int32_t ldx, int32_t C,
+                                          int32_t n_groups, const float* stats, float leak, int32_t act, float* dgamma, float* dbeta,
+                                          int32_t accumulate_param_grads, float* coef_out, void* ws, size_t ws_bytes, void* stream) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || ld_dy < C || ld_dpool < C || ((ld_dy | ld_dpool) & 3)) return MOPA_ERR_ARG;
+  if (C > 1024 || ldx < C || (ldx & 3) || !coef_out || n_groups < 1 || B % n_groups || (int64_t)B * H * W > INT32_MAX) return MOPA_ERR_ARG;
+  const int num_rows = B * H * W, n = num_rows / n_groups;
+  if (ws_bytes < mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
+  BnGroups grp;
+  if (!bn_make_groups(&grp, num_rows, n_groups, n, 2 * n)) return MOPA_ERR_ARG;
+  if ((size_t)grp.nblk_total * 2 * C * sizeof(float) > mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  float* partial = (float*)ws;
+  const int RL = 256 / (C >> 2);
+  const PoolBwdArgs pool{dpool, ld_dpool, argmax, H, W, (H + 1) / 2, (W + 1) / 2};
+  k_bn_bwd_partial_pool<<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(
+      pool, dy, ld_dy, accumulate_dy, x, ldx, C, stats, leak, act, grp, partial);
+  k_bn_bwd_finalize<<<C, 256, 0, st>>>(partial, grp, C, dgamma, dbeta, accumulate_param_grads, coef_out);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
 MOPA_API int mopa_bn_act_bwd(const float* dy, int32_t ld_dy, const float* x, int32_t ldx, float* dx, int32_t ld_dx,
                              int32_t num_rows, int32_t C, const float* stats, float leak, int32_t act,
                              const float* ymask, int32_t ld_ym, float* dres, int32_t ld_dres, int32_t accumulate_dres,

@@ -642,6 +642,21 @@ DEFER_STEM_BN = os.environ.get("MOPA_DEFER_STEM_BN", "1") != "0"   # ... and the
 # A/B switch: the stem BatchNorm's backward apply inside the stem's weight gradient (mopa_stem_bwd_weight_bn: dx is never written)
 # (the stem's weight gradient with the BatchNorm backward formed in its loader exists as an MFMA kernel only: off with MOPA_CONV2D_MFMA=0)
 STEM_BN_FUSED_BWD = os.environ.get("MOPA_STEM_BN_FUSED_BWD", "1") != "0" and os.environ.get("MOPA_CONV2D_MFMA", "1") != "0"
+# A/B switch: the second form of that tail (MOPA_STEM_BWD2: 1 = both parts, 0 = neither, "wgrad" / "pool" = one of them).  "pool": the
+# max-pool's backward inside the stem BatchNorm's sums pass (mopa_bn_bwd_sums_groups_pool forms, uses and writes the pooled share of dy:
+# no launch of its own, one pass less over the stem-resolution gradient).  "wgrad": the weight gradient from an image strip in LDS
+# (mopa_stem_bwd_weight_bn2) whose ordered slab reduction writes the parameter gradient's layout.  Same bits as the calls they replace;
+# only where STEM_BN_FUSED_BWD applies (not with want_dimg, a synchronised BatchNorm or MOPA_CONV2D_MFMA=0).
+STEM_BWD2 = frozenset({"1": ("wgrad", "pool"), "0": ()}.get(os.environ.get("MOPA_STEM_BWD2", "1"), (os.environ.get("MOPA_STEM_BWD2"),)))
+# (stem pixels B * Hp * Wp from which the second form is dispatched: one 302 x 480 image = 145,920 is inside, as is every training
+# batch; measured at 16 x 304 x 480, profiles/r12_stem_bwd.md.  Below it the tail is a few launches of some microseconds and keeps
+# the first form's calls)
+STEM_BWD2_MIN_PIXELS = int(os.environ.get("MOPA_STEM_BWD2_MIN_PIXELS", str(1 << 17)))
+
+
+def stem_bwd2(part, B, H, W):
+    """Does `part` ("wgrad" / "pool") of the second form of the stem's backward tail run on a B x H x W stem grid?"""
+    return part in STEM_BWD2 and STEM_BN_FUSED_BWD and B * H * W >= STEM_BWD2_MIN_PIXELS
 # A/B switch: the residual BatchNorms (bn2 of every BasicBlock) leave one bit per element, pre-activation > 0, and their backward pass
 # reads that bit instead of the whole saved output (mopa_bn_act_fwd_groups_bits / mopa_bn_act_bwd_groups_fused)
 BN_MASK_BITS = os.environ.get("MOPA_BN_MASK_BITS", "1") != "0"
@@ -932,6 +947,7 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
     # outputs of the convolutions with a bias: a BatchNorm that reads one leaves the partial column sums of its dx for the bias gradient
     biased = {key(r[4]) for r in tape if r[0] in ("conv", "convT") and r[2].b is not None} if BN_COLSUM_FUSED else set()
     db_partials = {}
+    pool_deferred = {}   # key of a max-pool's input -> (dy, argmax, accumulate): its backward runs inside the next BatchNorm backward
     for rec in reversed(tape):
         kind = rec[0]
         if kind == "bn":
@@ -947,15 +963,26 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
                     dres = like(res)
                     gmap[k] = dres
             (dg, db), pacc = sink.take(name + ".weight", name + ".bias")
-            if (STEM_BN_FUSED_BWD and name == pre + "bn1" and not want_dimg and res is None and act == 1
-                    and all(gt is None for gt in gathered) and x.C == 64):
+            pool = pool_deferred.pop(key(y), None)   # (the max-pool's backward into dy is still to run: see "maxpool" below)
+            stem_fused = (STEM_BN_FUSED_BWD and name == pre + "bn1" and not want_dimg and res is None and act == 1
+                          and all(gt is None for gt in gathered) and x.C == 64)
+            if pool is not None and not stem_fused:
+                pdy, amax, pacc_dy = pool
+                call("mopa_maxpool3x3s2_bwd", pdy.p, pdy.ld, ptr(amax), x.B, x.H, x.W, x.C, dy.p, dy.ld, int(pacc_dy), stream())
+                pool = None
+            if stem_fused:
                 # the stem's BatchNorm: its input gradient has ONE reader, the stem's weight gradient, which forms it from (dy, x)
                 # itself -- sums + parameter gradients here, no apply pass, no dx tensor
                 n = x.rows // G
                 coef = torch.empty(G, 2, x.C, dtype=torch.float32, device=dev)
                 ws = workspace.get(query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C), dev)
-                call("mopa_bn_bwd_sums_groups", dy.p, dy.ld, x.p, x.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act), None, 0,
-                     ptr(dg), ptr(db), int(pacc), ptr(coef), ptr(ws), ws.numel(), stream())
+                if pool is not None:   # ... and the sums pass forms the max-pool's share of dy on its way
+                    pdy, amax, pacc_dy = pool
+                    call("mopa_bn_bwd_sums_groups_pool", pdy.p, pdy.ld, ptr(amax), x.B, x.H, x.W, dy.p, dy.ld, int(pacc_dy), x.p, x.ld,
+                         x.C, G, ptr(stats), 0.0, int(act), ptr(dg), ptr(db), int(pacc), ptr(coef), ptr(ws), ws.numel(), stream())
+                else:
+                    call("mopa_bn_bwd_sums_groups", dy.p, dy.ld, x.p, x.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act), None, 0,
+                         ptr(dg), ptr(db), int(pacc), ptr(coef), ptr(ws), ws.numel(), stream())
                 gmap[key(x)] = ("bn", dy, x, stats, coef)
                 continue
             dx = like(x)
@@ -1015,7 +1042,11 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
             acc = k in gmap
             dx = gmap[k] if acc else like(x)
             gmap[k] = dx
-            call("mopa_maxpool3x3s2_bwd", dy.p, dy.ld, ptr(amax), x.B, x.H, x.W, x.C, dx.p, dx.ld, int(acc), stream())
+            if stem_bwd2("pool", x.B, x.H, x.W) and not want_dimg and hasattr(x, "bn"):
+                # the pool input is the stem's deferred BatchNorm, whose backward comes next and reads every element of dx: left to it
+                pool_deferred[k] = (dy, amax, acc)
+            else:
+                call("mopa_maxpool3x3s2_bwd", dy.p, dy.ld, ptr(amax), x.B, x.H, x.W, x.C, dx.p, dx.ld, int(acc), stream())
         elif kind == "stem":
             _, x4, c1, g = rec
             dout = gmap.pop(key(c1))
@@ -1023,18 +1054,24 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
             lazy = dout if isinstance(dout, tuple) else None   # ("bn", dy, x, stats, coef): the BatchNorm above left its apply to us
             # (the weight-gradient stream reads dy and, fused, the small coef tensor: both are dropped here before the streams are joined)
             with _on(wgrad_stream(dev), (lazy[1] if lazy else dout).t, *((lazy[4],) if lazy else ())):
-                dwl = torch.empty(7, 2, 16, 64, dtype=torch.float32, device=dev)
-                if lazy:
+                if lazy and stem_bwd2("wgrad", B, Hp, Wp):   # the strip kernel; its slab reduction writes dw itself (flags bit 1)
                     _, bdy, bx, bstats, bcoef = lazy
                     ws = workspace.get(query("mopa_conv2d_wgrad_workspace_bytes", ctypes.addressof(g)), dev)
-                    call("mopa_stem_bwd_weight_bn", ptr(x4), bdy.p, bdy.ld, bx.p, bx.ld, ptr(bstats), ptr(bcoef), G, int(training), ptr(dwl),
-                         ctypes.addressof(g), 0, ptr(ws), ws.numel(), stream())
+                    call("mopa_stem_bwd_weight_bn2", ptr(x4), bdy.p, bdy.ld, bx.p, bx.ld, ptr(bstats), ptr(bcoef), G, int(training), ptr(dw),
+                         ctypes.addressof(g), int(pacc) | 2, ptr(ws), ws.numel(), stream())
                 else:
-                    if g[24] != dout.ld:   # (forward wrote into a wider buffer; the gradient tensor has its own row stride)
-                        g = (ctypes.c_int32 * 25)(*g)
-                        g[24] = dout.ld
-                    wgrad(ptr(x4), dout.p, ptr(dwl), g, dev)
-                call("mopa_conv2d_stem_relayout", ptr(dwl), ptr(dw), 64, 1, int(pacc), stream())
+                    dwl = torch.empty(7, 2, 16, 64, dtype=torch.float32, device=dev)
+                    if lazy:
+                        _, bdy, bx, bstats, bcoef = lazy
+                        ws = workspace.get(query("mopa_conv2d_wgrad_workspace_bytes", ctypes.addressof(g)), dev)
+                        call("mopa_stem_bwd_weight_bn", ptr(x4), bdy.p, bdy.ld, bx.p, bx.ld, ptr(bstats), ptr(bcoef), G, int(training), ptr(dwl),
+                             ctypes.addressof(g), 0, ptr(ws), ws.numel(), stream())
+                    else:
+                        if g[24] != dout.ld:   # (forward wrote into a wider buffer; the gradient tensor has its own row stride)
+                            g = (ctypes.c_int32 * 25)(*g)
+                            g[24] = dout.ld
+                        wgrad(ptr(x4), dout.p, ptr(dwl), g, dev)
+                    call("mopa_conv2d_stem_relayout", ptr(dwl), ptr(dw), 64, 1, int(pacc), stream())
             if want_dimg:   # gradient w.r.t. the image itself (not asked for by MoPA's training)
                 dimg = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
                 call("mopa_stem_dgrad_image", dout.p, dout.ld, B, Hp, Wp, H, W, ptr(P[pre + "conv1.weight"]), ptr(dimg), stream())
