@@ -6,6 +6,7 @@
 // after it), :30 (OutputLayer); mopa/models/xmuda_arch.py:102,107,116,124 (linear heads).
 // Semantics: SURVEY.md Appendix A.2, A.3, A.6; oracle: oracle/scn3d.py::{input_layer,output_layer,bn_relu}.
 #include "common.h"
+#include <initializer_list>
 
 // Rows handled by one block of the two-stage reductions: enough blocks to fill 256 CUs several times over even for
 // the short-and-wide tensors of the deep layers (e.g. 4,560 rows x 512 channels), capped at 1024 rows.
@@ -45,34 +46,28 @@ static inline bool bn_make_groups(BnGroups* g, int num_rows, int n_groups, int s
   }
   return true;
 }
-
-// ------------------------------------------------------------------------------------------ BN statistics
-// partial[blk][0][c] = sum(x - x0), partial[blk][1][c] = sum((x - x0)^2) with x0 = first row (shifted sums keep
-// fp32 accurate when |mean| >> std).  C % 4 == 0.
-__global__ __launch_bounds__(256) void k_bn_stats_partial(const float* __restrict__ x, int ld, int C, const BnGroups grp,
-                                                           float* __restrict__ partial) {
-  extern __shared__ float lds[];  // [2][RL][C]
+// The block of a partial-sum kernel (grid = blocks x groups, 256 threads, LDS [2][RL][C]): thread (rl, cq) walks the rows rbeg + rl,
+// += RL below rend of channel quad cq; `partial` is the group's slab.  bn_block_begin -> false: the group has no such block.
+struct BnBlock { int C, RL, cq, rl, rbeg, rend; float* partial; };
+__device__ __forceinline__ bool bn_block_begin(const BnGroups& grp, int C, float* __restrict__ partial, BnBlock& b) {
   const int gi = blockIdx.y;
-  if ((int)blockIdx.x >= grp.nblk[gi]) return;
+  if ((int)blockIdx.x >= grp.nblk[gi]) return false;
   const int CQ = C >> 2;
-  const int RL = 256 / CQ;
-  const int cq = threadIdx.x % CQ, rl = threadIdx.x / CQ;
+  b.C = C; b.RL = 256 / CQ;
+  b.cq = threadIdx.x % CQ; b.rl = threadIdx.x / CQ;
   const int rpb = grp.rpb[gi];
-  const int rbeg = grp.row0[gi] + blockIdx.x * rpb, rend = min(grp.row0[gi] + grp.rows[gi], rbeg + rpb);
-  partial += (int64_t)grp.poff[gi] * 2 * C;
-  float s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
-  if (rl < RL) {
-    const float4 k = *reinterpret_cast<const float4*>(x + (int64_t)grp.row0[gi] * ld + cq * 4);
-    for (int row = rbeg + rl; row < rend; row += RL) {
-      const float4 v = *reinterpret_cast<const float4*>(x + (int64_t)row * ld + cq * 4);
-      float d0 = v.x - k.x, d1 = v.y - k.y, d2 = v.z - k.z, d3 = v.w - k.w;
-      s[0] += d0; s[1] += d1; s[2] += d2; s[3] += d3;
-      ss[0] += d0 * d0; ss[1] += d1 * d1; ss[2] += d2 * d2; ss[3] += d3 * d3;
-    }
+  b.rbeg = grp.row0[gi] + blockIdx.x * rpb; b.rend = min(grp.row0[gi] + grp.rows[gi], b.rbeg + rpb);
+  b.partial = partial + (int64_t)grp.poff[gi] * 2 * C;
+  return true;
+}
+// The thread's two sums to LDS, the RL row lanes added in order, partial[block][2][C] written.
+__device__ __forceinline__ void bn_block_end(const BnBlock& b, float* __restrict__ lds, const float (&s)[4], const float (&ss)[4]) {
+  const int C = b.C, RL = b.RL;
+  if (b.rl < RL) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      lds[(0 * RL + rl) * C + cq * 4 + j] = s[j];
-      lds[(1 * RL + rl) * C + cq * 4 + j] = ss[j];
+      lds[(0 * RL + b.rl) * C + b.cq * 4 + j] = s[j];
+      lds[(1 * RL + b.rl) * C + b.cq * 4 + j] = ss[j];
     }
   }
   __syncthreads();
@@ -80,8 +75,29 @@ __global__ __launch_bounds__(256) void k_bn_stats_partial(const float* __restric
     const int which = i / C, c = i - which * C;
     float t = 0.f;
     for (int k = 0; k < RL; ++k) t += lds[(which * RL + k) * C + c];
-    partial[(int64_t)blockIdx.x * 2 * C + i] = t;
+    b.partial[(int64_t)blockIdx.x * 2 * C + i] = t;
   }
+}
+
+// ------------------------------------------------------------------------------------------ BN statistics
+// partial[blk][0][c] = sum(x - x0), partial[blk][1][c] = sum((x - x0)^2) with x0 = first row (shifted sums keep
+// fp32 accurate when |mean| >> std).  C % 4 == 0.
+__global__ __launch_bounds__(256) void k_bn_stats_partial(const float* __restrict__ x, int ld, int C, const BnGroups grp,
+                                                           float* __restrict__ partial) {
+  extern __shared__ float lds[];  // [2][RL][C]
+  BnBlock b;
+  if (!bn_block_begin(grp, C, partial, b)) return;
+  float s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+  if (b.rl < b.RL) {
+    const float4 k = *reinterpret_cast<const float4*>(x + (int64_t)grp.row0[blockIdx.y] * ld + b.cq * 4);
+    for (int row = b.rbeg + b.rl; row < b.rend; row += b.RL) {
+      const float4 v = *reinterpret_cast<const float4*>(x + (int64_t)row * ld + b.cq * 4);
+      float d0 = v.x - k.x, d1 = v.y - k.y, d2 = v.z - k.z, d3 = v.w - k.w;
+      s[0] += d0; s[1] += d1; s[2] += d2; s[3] += d3;
+      ss[0] += d0 * d0; ss[1] += d1 * d1; ss[2] += d2 * d2; ss[3] += d3 * d3;
+    }
+  }
+  bn_block_end(b, lds, s, ss);
 }
 
 // One block of 256 per channel: the threads stride over the block partials (<= 8 independent loads each; one wave per channel
@@ -209,6 +225,20 @@ MOPA_API size_t mopa_bnrelu_rows_workspace_bytes(int32_t num_rows, int32_t C) {
   if (nb < bn_num_blocks(num_rows)) nb = bn_num_blocks(num_rows);
   return align_up((size_t)nb * 2 * C * sizeof(float), 256);
 }
+// What the launchers of the grouped two-stage reductions check before their first launch, in this order: rows and channels, the row
+// stride of every tensor handed in (an absent optional tensor: pass C), the workspace against ws_need, the groups, and that the partial
+// slabs of all groups fit in front of the coefficient block (rows per block stop growing at 1024, so groups of more than 2 M rows hold
+// more blocks than the workspace's cap of 3 x 2048).  ws_need = 0: no workspace test here (the forward pass tests its own, see there).
+static int bn_check(BnGroups* grp, int num_rows, int C, int n_groups, int split1, int split2, std::initializer_list<int> strides,
+                    size_t ws_bytes, size_t ws_need) {
+  if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024) return MOPA_ERR_ARG;
+  for (int ld : strides)
+    if (ld < C || (ld & 3)) return MOPA_ERR_ARG;
+  if (ws_bytes < ws_need) return MOPA_ERR_WORKSPACE;
+  if (!bn_make_groups(grp, num_rows, n_groups, split1, split2)) return MOPA_ERR_ARG;
+  if (ws_need && (size_t)grp->nblk_total * 2 * C * sizeof(float) > mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
+  return MOPA_OK;
+}
 
 // y = act(batchnorm(x) (+ res)).  stats[4][C] receives scale, shift, mean, invstd (saved for backward).
 // act: 0 identity / 1 leaky-ReLU(leak).  res (optional) is added before the activation (ResNet BasicBlock tail).
@@ -222,16 +252,14 @@ static int bn_act_fwd_groups(const float* x, int32_t ldx, float* y, int32_t ldy,
                              const float* gamma, const float* beta, float* running_mean, float* running_var,
                              float momentum, float eps, float leak, int32_t act, const float* res, int32_t ld_res,
                              int32_t training, float* stats, uint32_t* bits, void* ws, size_t ws_bytes, void* stream) {
-  if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ldx < C || (ldx & 3) || (y && (ldy < C || (ldy & 3)))) return MOPA_ERR_ARG;
-  if (res && (ld_res < C || (ld_res & 3) || !y)) return MOPA_ERR_ARG;
+  if (res && !y) return MOPA_ERR_ARG;
   BnGroups grp;
-  if (!bn_make_groups(&grp, num_rows, n_groups, split1, split2)) return MOPA_ERR_ARG;
+  if (int rc = bn_check(&grp, num_rows, C, n_groups, split1, split2, {ldx, y ? ldy : C, res ? ld_res : C}, ws_bytes, 0)) return rc;
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
-  if (training) {
+  if (training) {   // (the one workspace test of the forward pass: what its slabs take, whatever the query function says)
     if (ws_bytes < (size_t)grp.nblk_total * 2 * C * sizeof(float)) return MOPA_ERR_WORKSPACE;
     const int RL = 256 / (C >> 2);
-    if (RL < 1) return MOPA_ERR_ARG;
     k_bn_stats_partial<<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(x, ldx, C, grp, partial);
   }
   k_bn_finalize<<<C, 256, 0, st>>>(partial, grp, x, ldx, C, gamma, beta, running_mean, running_var, momentum, eps, training, stats);
@@ -307,25 +335,116 @@ __device__ __forceinline__ uint32_t bn_mask_nibble(const uint32_t* __restrict__ 
   return bits[row * (C >> 5) + (cq >> 3)] >> ((cq & 7) * 4);
 }
 
-// BITS: the activation mask is the forward pass's bit per element (`bits`, layout at k_bn_relu_apply) instead of the saved output.
-template <bool BITS>
-__global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict__ dy, int ld_dy,
-                                                         const float* __restrict__ x, int ldx, int C,
-                                                         const float* __restrict__ stats, float leak,
-                                                         const float* __restrict__ ymask, int ld_ym, int act, const BnGroups grp,
-                                                         float* __restrict__ partial, const uint32_t* __restrict__ bits) {
+// The three row sources of k_bn_bwd_partial: load() issues a row's loads of dy and of its activation mask into registers, value() gives
+// the row's dy from them, dz() the masked gradient of element j.
+//   BnRowsMask  dy as stored; the mask from the saved output (ymask) or, ymask == null, recomputed from x
+//   BnRowsBits  dy as stored; the mask is the forward pass's bit per element (`bits`, layout at k_bn_relu_apply)
+//   BnRowsPool  dy formed from the max-pool's backward and written back (see PoolBwdArgs); the mask recomputed from x
+struct BnRowsMask {
+  const float* __restrict__ dy; int ld_dy; const float* __restrict__ ymask; int ld_ym;
+  struct Row { float4 g, y; };
+  __device__ __forceinline__ void load(int row, int cq, int C, Row& r) const {
+    r.g = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
+    r.y = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ymask) r.y = *reinterpret_cast<const float4*>(ymask + (int64_t)row * ld_ym + cq * 4);
+  }
+  __device__ __forceinline__ float4 value(int row, int cq, const Row& r) const { return r.g; }
+  __device__ __forceinline__ float dz(int j, float g, float xv, float sc, float sh, float leak, int act, const Row& r) const {
+    const float ys[4] = {r.y.x, r.y.y, r.y.z, r.y.w};
+    return bn_dz(g, xv, sc, sh, leak, act, ymask != nullptr, ys[j]);
+  }
+};
+struct BnRowsBits {
+  const float* __restrict__ dy; int ld_dy; const uint32_t* __restrict__ bits;
+  struct Row { float4 g; uint32_t m; };
+  __device__ __forceinline__ void load(int row, int cq, int C, Row& r) const {
+    r.g = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
+    r.m = bn_mask_nibble(bits, row, C, cq);
+  }
+  __device__ __forceinline__ float4 value(int row, int cq, const Row& r) const { return r.g; }
+  __device__ __forceinline__ float dz(int j, float g, float xv, float sc, float sh, float leak, int act, const Row& r) const {
+    return bn_dz_bit(g, leak, act, (r.m >> j) & 1u);
+  }
+};
+// What the pool source (BnRowsPool below) loads and forms.  Its dy is a tensor that a 3x3 / stride 2 / padding 1 max-pool's backward
+// still has to add its share to: row (b, iy, ix) of dy is formed here -- the up to four pooling windows over the pixel in
+// k_maxpool_bwd's order (window row, then window column, from 0.f), then the value dy already holds when `accumulate` -- used for
+// the sums and written back, so the tensor gets k_maxpool_bwd's bits without that kernel's pass over it.  Loads are unconditional:
+// a window that does not cover the pixel (or lies outside the pooled map) re-reads the pixel's first window and its tap code is one
+// no argmax byte takes.
+struct PoolBwdArgs { const float* dpool; int ld_dpool; const unsigned char* argmax; int H, W, OH, OW; };
+struct PoolRow { float4 g[4]; uchar4 w[4]; float4 q; int tap[4]; };
+__device__ __forceinline__ void pool_bwd_row_load(const PoolBwdArgs& p, const float* __restrict__ dy, int ld_dy, int C, int row, int cq,
+                                                  bool accumulate, PoolRow& o) {
+  const int ix = row % p.W, r = row / p.W;
+  const int iy = r % p.H, b = r / p.H;
+  const int by = iy >> 1, py = iy & 1, bx = ix >> 1, px = ix & 1;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const bool ok = a <= py && c <= px && by + a < p.OH && bx + c < p.OW;
+      const int64_t w = (int64_t)(b * p.OH + by + (ok ? a : 0)) * p.OW + bx + (ok ? c : 0);
+      o.tap[a * 2 + c] = ok ? (a == 0 ? 1 + py : 0) * 3 + (c == 0 ? 1 + px : 0) : 255;
+      o.w[a * 2 + c] = *reinterpret_cast<const uchar4*>(p.argmax + w * C + cq * 4);
+      o.g[a * 2 + c] = *reinterpret_cast<const float4*>(p.dpool + w * p.ld_dpool + cq * 4);
+    }
+  o.q = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (accumulate) o.q = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
+}
+__device__ __forceinline__ float4 pool_bwd_row_value(const PoolRow& o, bool accumulate) {
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    s[0] = o.w[k].x == o.tap[k] ? s[0] + o.g[k].x : s[0];
+    s[1] = o.w[k].y == o.tap[k] ? s[1] + o.g[k].y : s[1];
+    s[2] = o.w[k].z == o.tap[k] ? s[2] + o.g[k].z : s[2];
+    s[3] = o.w[k].w == o.tap[k] ? s[3] + o.g[k].w : s[3];
+  }
+  if (accumulate) { s[0] += o.q.x; s[1] += o.q.y; s[2] += o.q.z; s[3] += o.q.w; }
+  return make_float4(s[0], s[1], s[2], s[3]);
+}
+struct BnRowsPool {
+  PoolBwdArgs pool; float* dy; int ld_dy; bool accumulate;
+  typedef PoolRow Row;
+  __device__ __forceinline__ void load(int row, int cq, int C, Row& r) const { pool_bwd_row_load(pool, dy, ld_dy, C, row, cq, accumulate, r); }
+  __device__ __forceinline__ float4 value(int row, int cq, const Row& r) const {
+    const float4 gv = pool_bwd_row_value(r, accumulate);
+    *reinterpret_cast<float4*>(dy + (int64_t)row * ld_dy + cq * 4) = gv;
+    return gv;
+  }
+  __device__ __forceinline__ float dz(int j, float g, float xv, float sc, float sh, float leak, int act, const Row& r) const {
+    return bn_dz(g, xv, sc, sh, leak, act, false, 0.f);
+  }
+};
+
+// One row into the sums of thread (., cq): every row of k_bn_bwd_partial goes through here, in row order.
+// (A __forceinline__ function, not a lambda in the kernel: as a lambda it is inlined at a later stage than the prologue and epilogue, and
+// the mask source then takes 98 VGPRs and 4 waves per SIMD instead of 96 and 5.)
+template <class Src>
+__device__ __forceinline__ void bn_bwd_add_row(const Src& src, int row, int cq, const float4& xv, const typename Src::Row& r,
+                                               const float (&sc)[4], const float (&sh)[4], const float (&mu)[4], const float (&is)[4],
+                                               float leak, int act, float (&s)[4], float (&ss)[4]) {
+  const float4 gv = src.value(row, cq, r);
+  const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float dz = src.dz(j, gs[j], xs[j], sc[j], sh[j], leak, act, r);
+    s[j] += dz;
+    ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
+  }
+}
+template <class Src>
+__global__ __launch_bounds__(256) void k_bn_bwd_partial(const Src src, const float* __restrict__ x, int ldx, int C,
+                                                         const float* __restrict__ stats, float leak, int act, const BnGroups grp,
+                                                         float* __restrict__ partial) {
   extern __shared__ float lds[];
-  const int gi = blockIdx.y;
-  if ((int)blockIdx.x >= grp.nblk[gi]) return;
-  const int CQ = C >> 2;
-  const int RL = 256 / CQ;
-  const int cq = threadIdx.x % CQ, rl = threadIdx.x / CQ;
-  const int rpb = grp.rpb[gi];
-  const int rbeg = grp.row0[gi] + blockIdx.x * rpb, rend = min(grp.row0[gi] + grp.rows[gi], rbeg + rpb);
-  partial += (int64_t)grp.poff[gi] * 2 * C;
-  stats += (int64_t)gi * 4 * C;
+  BnBlock b;
+  if (!bn_block_begin(grp, C, partial, b)) return;
+  stats += (int64_t)blockIdx.y * 4 * C;
+  const int cq = b.cq, RL = b.RL, rend = b.rend;
   float s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
-  if (rl < RL) {
+  if (b.rl < RL) {
     float sc[4], sh[4], mu[4], is[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -333,60 +452,26 @@ __global__ __launch_bounds__(256) void k_bn_bwd_partial(const float* __restrict_
       mu[j] = stats[2 * C + cq * 4 + j]; is[j] = stats[3 * C + cq * 4 + j];
     }
     // four rows of loads in flight per thread (the sums take the rows in the same order as a rolled loop: same bits)
-    int row = rbeg + rl;
+    int row = b.rbeg + b.rl;
     for (; row + 3 * RL < rend; row += 4 * RL) {
-      float4 xv[4], gv[4], yv[4];
-      uint32_t mw[4];
+      float4 xv[4];
+      typename Src::Row r[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         xv[u] = *reinterpret_cast<const float4*>(x + (int64_t)(row + u * RL) * ldx + cq * 4);
-        gv[u] = *reinterpret_cast<const float4*>(dy + (int64_t)(row + u * RL) * ld_dy + cq * 4);
-        yv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        mw[u] = 0u;
-        if (BITS) mw[u] = bn_mask_nibble(bits, row + u * RL, C, cq);
-        else if (ymask) yv[u] = *reinterpret_cast<const float4*>(ymask + (int64_t)(row + u * RL) * ld_ym + cq * 4);
+        src.load(row + u * RL, cq, C, r[u]);
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w}, gs[4] = {gv[u].x, gv[u].y, gv[u].z, gv[u].w}, ys[4] = {yv[u].x, yv[u].y, yv[u].z, yv[u].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float dz = BITS ? bn_dz_bit(gs[j], leak, act, (mw[u] >> j) & 1u)
-                                : bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
-          s[j] += dz;
-          ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
-        }
-      }
+      for (int u = 0; u < 4; ++u) bn_bwd_add_row(src, row + u * RL, cq, xv[u], r[u], sc, sh, mu, is, leak, act, s, ss);
     }
     for (; row < rend; row += RL) {
       const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)row * ldx + cq * 4);
-      const float4 gv = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
-      float4 yv = make_float4(0.f, 0.f, 0.f, 0.f);
-      uint32_t mw = 0u;
-      if (BITS) mw = bn_mask_nibble(bits, row, C, cq);
-      else if (ymask) yv = *reinterpret_cast<const float4*>(ymask + (int64_t)row * ld_ym + cq * 4);
-      const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float dz = BITS ? bn_dz_bit(gs[j], leak, act, (mw >> j) & 1u)
-                              : bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, ymask != nullptr, ys[j]);
-        s[j] += dz;
-        ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      lds[(0 * RL + rl) * C + cq * 4 + j] = s[j];
-      lds[(1 * RL + rl) * C + cq * 4 + j] = ss[j];
+      typename Src::Row r;
+      src.load(row, cq, C, r);
+      bn_bwd_add_row(src, row, cq, xv, r, sc, sh, mu, is, leak, act, s, ss);
     }
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += 256) {
-    const int which = i / C, c = i - which * C;
-    float t = 0.f;
-    for (int k = 0; k < RL; ++k) t += lds[(which * RL + k) * C + c];
-    partial[(int64_t)blockIdx.x * 2 * C + i] = t;
-  }
+  bn_block_end(b, lds, s, ss);
 }
 
 // dgamma/dbeta (+= if accumulate) and the two per-channel means used by the apply pass (coef[2][C]).
@@ -546,16 +631,11 @@ static int bn_act_bwd_groups(const float* dy, int32_t ld_dy, const float* x, int
                              int32_t ld_dres, int32_t accumulate_dres, int32_t training, float* dgamma, float* dbeta,
                              int32_t accumulate_param_grads, int32_t accumulate_dx, float* colsum_partial, void* ws, size_t ws_bytes,
                              void* stream) {
-  if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ldx < C || ld_dy < C || ld_dx < C || ((ldx | ld_dy | ld_dx) & 3))
-    return MOPA_ERR_ARG;
-  if ((ymask && (ld_ym < C || (ld_ym & 3))) || (dres && (ld_dres < C || (ld_dres & 3)))) return MOPA_ERR_ARG;
   if (bits && ((C & 31) || leak != 0.f)) return MOPA_ERR_ARG;
-  if (ws_bytes < mopa_bnrelu_rows_bwd_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
   BnGroups grp;
-  if (!bn_make_groups(&grp, num_rows, n_groups, split1, split2)) return MOPA_ERR_ARG;
-  // the partial slabs of all groups must fit in front of the coefficient block (rows per block stop growing at 1024, so groups of
-  // more than 2 M rows hold more blocks than the workspace's cap of 3 x 2048: the forward refuses the same case)
-  if ((size_t)grp.nblk_total * 2 * C * sizeof(float) > mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
+  if (int rc = bn_check(&grp, num_rows, C, n_groups, split1, split2, {ldx, ld_dy, ld_dx, ymask ? ld_ym : C, dres ? ld_dres : C}, ws_bytes,
+                        mopa_bnrelu_rows_bwd_workspace_bytes(num_rows, C)))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
   float* coef = (float*)((char*)ws + mopa_bnrelu_rows_workspace_bytes(num_rows, C));
@@ -563,9 +643,9 @@ static int bn_act_bwd_groups(const float* dy, int32_t ld_dy, const float* x, int
   const dim3 pgrid(grp.nblk_max, grp.n);
   const size_t plds = (size_t)2 * RL * C * sizeof(float);
   if (bits)
-    k_bn_bwd_partial<true><<<pgrid, 256, plds, st>>>(dy, ld_dy, x, ldx, C, stats, leak, nullptr, 0, act, grp, partial, bits);
+    k_bn_bwd_partial<<<pgrid, 256, plds, st>>>(BnRowsBits{dy, ld_dy, bits}, x, ldx, C, stats, leak, act, grp, partial);
   else
-    k_bn_bwd_partial<false><<<pgrid, 256, plds, st>>>(dy, ld_dy, x, ldx, C, stats, leak, ymask, ld_ym, act, grp, partial, nullptr);
+    k_bn_bwd_partial<<<pgrid, 256, plds, st>>>(BnRowsMask{dy, ld_dy, ymask, ld_ym}, x, ldx, C, stats, leak, act, grp, partial);
   k_bn_bwd_finalize<<<C, 256, 0, st>>>(partial, grp, C, dgamma, dbeta, accumulate_param_grads, coef);
   const BnApplyArgs aa = {dy, ld_dy, x, ldx, dx, ld_dx, bits ? nullptr : ymask, ld_ym, bits, dres, ld_dres,
                           leak, training, accumulate_dx, act, accumulate_dres, C};
@@ -623,153 +703,39 @@ MOPA_API int mopa_bn_bwd_sums_groups(const float* dy, int32_t ld_dy, const float
                                      int32_t n_groups, int32_t split1, int32_t split2, const float* stats, float leak, int32_t act,
                                      const float* ymask, int32_t ld_ym, float* dgamma, float* dbeta, int32_t accumulate_param_grads,
                                      float* coef_out, void* ws, size_t ws_bytes, void* stream) {
-  if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ldx < C || ld_dy < C || ((ldx | ld_dy) & 3) || !coef_out) return MOPA_ERR_ARG;
-  if (ymask && (ld_ym < C || (ld_ym & 3))) return MOPA_ERR_ARG;
-  if (ws_bytes < mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
+  if (!coef_out) return MOPA_ERR_ARG;
   BnGroups grp;
-  if (!bn_make_groups(&grp, num_rows, n_groups, split1, split2)) return MOPA_ERR_ARG;
-  if ((size_t)grp.nblk_total * 2 * C * sizeof(float) > mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
+  if (int rc = bn_check(&grp, num_rows, C, n_groups, split1, split2, {ldx, ld_dy, ymask ? ld_ym : C}, ws_bytes,
+                        mopa_bnrelu_rows_workspace_bytes(num_rows, C)))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
   const int RL = 256 / (C >> 2);
-  k_bn_bwd_partial<false><<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(
-      dy, ld_dy, x, ldx, C, stats, leak, ymask, ld_ym, act, grp, partial, nullptr);
+  k_bn_bwd_partial<<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(
+      BnRowsMask{dy, ld_dy, ymask, ld_ym}, x, ldx, C, stats, leak, act, grp, partial);
   k_bn_bwd_finalize<<<C, 256, 0, st>>>(partial, grp, C, dgamma, dbeta, accumulate_param_grads, coef_out);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }
-// k_bn_bwd_partial (saved-output mask recomputed from x) over a dy that a 3x3 / stride 2 / padding 1 max-pool's backward still has to
-// add its share to: row (b, iy, ix) of dy is formed here -- the up to four pooling windows over the pixel in k_maxpool_bwd's order
-// (window row, then window column, from 0.f), then the value dy already holds when `accumulate` -- used for the sums and written back,
-// so the tensor gets k_maxpool_bwd's bits without that kernel's pass over it.  Same block partition, same row order per thread, same
-// LDS pass as k_bn_bwd_partial: same partial sums.  Loads are unconditional: a window that does not cover the pixel (or lies outside
-// the pooled map) re-reads the pixel's first window and its tap code is one no argmax byte takes.
-struct PoolBwdArgs { const float* dpool; int ld_dpool; const unsigned char* argmax; int H, W, OH, OW; };
-struct PoolRow { float4 g[4]; uchar4 w[4]; float4 q; int tap[4]; };
-__device__ __forceinline__ void pool_bwd_row_load(const PoolBwdArgs& p, const float* __restrict__ dy, int ld_dy, int C, int row, int cq,
-                                                  bool accumulate, PoolRow& o) {
-  const int ix = row % p.W, r = row / p.W;
-  const int iy = r % p.H, b = r / p.H;
-  const int by = iy >> 1, py = iy & 1, bx = ix >> 1, px = ix & 1;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const bool ok = a <= py && c <= px && by + a < p.OH && bx + c < p.OW;
-      const int64_t w = (int64_t)(b * p.OH + by + (ok ? a : 0)) * p.OW + bx + (ok ? c : 0);
-      o.tap[a * 2 + c] = ok ? (a == 0 ? 1 + py : 0) * 3 + (c == 0 ? 1 + px : 0) : 255;
-      o.w[a * 2 + c] = *reinterpret_cast<const uchar4*>(p.argmax + w * C + cq * 4);
-      o.g[a * 2 + c] = *reinterpret_cast<const float4*>(p.dpool + w * p.ld_dpool + cq * 4);
-    }
-  o.q = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (accumulate) o.q = *reinterpret_cast<const float4*>(dy + (int64_t)row * ld_dy + cq * 4);
-}
-__device__ __forceinline__ float4 pool_bwd_row_value(const PoolRow& o, bool accumulate) {
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    s[0] = o.w[k].x == o.tap[k] ? s[0] + o.g[k].x : s[0];
-    s[1] = o.w[k].y == o.tap[k] ? s[1] + o.g[k].y : s[1];
-    s[2] = o.w[k].z == o.tap[k] ? s[2] + o.g[k].z : s[2];
-    s[3] = o.w[k].w == o.tap[k] ? s[3] + o.g[k].w : s[3];
-  }
-  if (accumulate) { s[0] += o.q.x; s[1] += o.q.y; s[2] += o.q.z; s[3] += o.q.w; }
-  return make_float4(s[0], s[1], s[2], s[3]);
-}
-__global__ __launch_bounds__(256) void k_bn_bwd_partial_pool(const PoolBwdArgs pool, float* __restrict__ dy, int ld_dy, int accumulate_dy,
-                                                              const float* __restrict__ x, int ldx, int C,
-                                                              const float* __restrict__ stats, float leak, int act, const BnGroups grp,
-                                                              float* __restrict__ partial) {
-  extern __shared__ float lds[];
-  const int gi = blockIdx.y;
-  if ((int)blockIdx.x >= grp.nblk[gi]) return;
-  const int CQ = C >> 2;
-  const int RL = 256 / CQ;
-  const int cq = threadIdx.x % CQ, rl = threadIdx.x / CQ;
-  const int rpb = grp.rpb[gi];
-  const int rbeg = grp.row0[gi] + blockIdx.x * rpb, rend = min(grp.row0[gi] + grp.rows[gi], rbeg + rpb);
-  partial += (int64_t)grp.poff[gi] * 2 * C;
-  stats += (int64_t)gi * 4 * C;
-  float s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
-  if (rl < RL) {
-    float sc[4], sh[4], mu[4], is[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      sc[j] = stats[cq * 4 + j]; sh[j] = stats[C + cq * 4 + j];
-      mu[j] = stats[2 * C + cq * 4 + j]; is[j] = stats[3 * C + cq * 4 + j];
-    }
-    // four rows of loads in flight per thread, summed in row order (k_bn_bwd_partial)
-    int row = rbeg + rl;
-    for (; row + 3 * RL < rend; row += 4 * RL) {
-      float4 xv[4];
-      PoolRow pr[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        xv[u] = *reinterpret_cast<const float4*>(x + (int64_t)(row + u * RL) * ldx + cq * 4);
-        pool_bwd_row_load(pool, dy, ld_dy, C, row + u * RL, cq, accumulate_dy != 0, pr[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float4 gv = pool_bwd_row_value(pr[u], accumulate_dy != 0);
-        *reinterpret_cast<float4*>(dy + (int64_t)(row + u * RL) * ld_dy + cq * 4) = gv;
-        const float xs[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, false, 0.f);
-          s[j] += dz;
-          ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
-        }
-      }
-    }
-    for (; row < rend; row += RL) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + (int64_t)row * ldx + cq * 4);
-      PoolRow pr;
-      pool_bwd_row_load(pool, dy, ld_dy, C, row, cq, accumulate_dy != 0, pr);
-      const float4 gv = pool_bwd_row_value(pr, accumulate_dy != 0);
-      *reinterpret_cast<float4*>(dy + (int64_t)row * ld_dy + cq * 4) = gv;
-      const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, gs[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float dz = bn_dz(gs[j], xs[j], sc[j], sh[j], leak, act, false, 0.f);
-        s[j] += dz;
-        ss[j] += dz * ((xs[j] - mu[j]) * is[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      lds[(0 * RL + rl) * C + cq * 4 + j] = s[j];
-      lds[(1 * RL + rl) * C + cq * 4 + j] = ss[j];
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 2 * C; i += 256) {
-    const int which = i / C, c = i - which * C;
-    float t = 0.f;
-    for (int k = 0; k < RL; ++k) t += lds[(which * RL + k) * C + c];
-    partial[(int64_t)blockIdx.x * 2 * C + i] = t;
-  }
-}
 // mopa_maxpool3x3s2_bwd(dpool, argmax -> dy, accumulate_dy) followed by mopa_bn_bwd_sums_groups(dy, x; no saved-output mask) over the
-// B * H * W rows of the pool's input, as the sums pass alone (k_bn_bwd_partial_pool + k_bn_bwd_finalize): dy is left as the pool's
+// B * H * W rows of the pool's input, as the sums pass alone (k_bn_bwd_partial over BnRowsPool + k_bn_bwd_finalize): dy is left as the pool's
 // backward leaves it, dgamma / dbeta / coef_out as the sums call leaves them.  The B images are n_groups equal consecutive groups.
 // Refuses what either of the two calls refuses.
 MOPA_API int mopa_bn_bwd_sums_groups_pool(const float* dpool, int32_t ld_dpool, const uint8_t* argmax, int32_t B, int32_t H, int32_t W,
                                           float* dy, int32_t ld_dy, int32_t accumulate_dy, const float* x, int32_t ldx, int32_t C,
                                           int32_t n_groups, const float* stats, float leak, int32_t act, float* dgamma, float* dbeta,
                                           int32_t accumulate_param_grads, float* coef_out, void* ws, size_t ws_bytes, void* stream) {
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || ld_dy < C || ld_dpool < C || ((ld_dy | ld_dpool) & 3)) return MOPA_ERR_ARG;
-  if (C > 1024 || ldx < C || (ldx & 3) || !coef_out || n_groups < 1 || B % n_groups || (int64_t)B * H * W > INT32_MAX) return MOPA_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0 || !coef_out || n_groups < 1 || B % n_groups || (int64_t)B * H * W > INT32_MAX) return MOPA_ERR_ARG;
   const int num_rows = B * H * W, n = num_rows / n_groups;
-  if (ws_bytes < mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
   BnGroups grp;
-  if (!bn_make_groups(&grp, num_rows, n_groups, n, 2 * n)) return MOPA_ERR_ARG;
-  if ((size_t)grp.nblk_total * 2 * C * sizeof(float) > mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
+  if (int rc = bn_check(&grp, num_rows, C, n_groups, n, 2 * n, {ldx, ld_dy, ld_dpool}, ws_bytes, mopa_bnrelu_rows_workspace_bytes(num_rows, C)))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)ws;
   const int RL = 256 / (C >> 2);
   const PoolBwdArgs pool{dpool, ld_dpool, argmax, H, W, (H + 1) / 2, (W + 1) / 2};
-  k_bn_bwd_partial_pool<<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(
-      pool, dy, ld_dy, accumulate_dy, x, ldx, C, stats, leak, act, grp, partial);
+  k_bn_bwd_partial<<<dim3(grp.nblk_max, grp.n), 256, (size_t)2 * RL * C * sizeof(float), st>>>(
+      BnRowsPool{pool, dy, ld_dy, accumulate_dy != 0}, x, ldx, C, stats, leak, act, grp, partial);
   k_bn_bwd_finalize<<<C, 256, 0, st>>>(partial, grp, C, dgamma, dbeta, accumulate_param_grads, coef_out);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
@@ -852,14 +818,12 @@ __global__ void k_bn_finalize_sync(const double* __restrict__ gathered, int worl
 // moments: 2C+1 doubles (mean[C], M2[C], n) of this rank's rows.  ws as for mopa_bn_act_fwd.
 MOPA_API int mopa_bn_sync_moments(const float* x, int32_t ldx, int32_t num_rows, int32_t C, double* moments, void* ws, size_t ws_bytes,
                                   void* stream) {
-  if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ldx < C || (ldx & 3) || !moments) return MOPA_ERR_ARG;
-  if (ws_bytes < mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = bn_num_blocks(num_rows), RL = 256 / (C >> 2);
-  if (RL < 1) return MOPA_ERR_ARG;
-  float* partial = (float*)ws;
+  if (!moments) return MOPA_ERR_ARG;
   BnGroups one;
-  bn_make_groups(&one, num_rows, 1, 0, 0);
+  if (int rc = bn_check(&one, num_rows, C, 1, 0, 0, {ldx}, ws_bytes, mopa_bnrelu_rows_workspace_bytes(num_rows, C))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = one.nblk[0], RL = 256 / (C >> 2);
+  float* partial = (float*)ws;
   k_bn_stats_partial<<<nblk, 256, (size_t)2 * RL * C * sizeof(float), st>>>(x, ldx, C, one, partial);
   k_bn_local_moments<<<C, 256, 0, st>>>(partial, nblk, x, num_rows, C, moments);
   MOPA_CHECK_LAUNCH();
@@ -913,16 +877,15 @@ __global__ void k_bn_bwd_coef_sync(const double* __restrict__ sums, const double
 MOPA_API int mopa_bn_sync_bwd_sums(const float* dy, int32_t ld_dy, const float* x, int32_t ldx, int32_t num_rows, int32_t C,
                                    const float* stats, float leak, int32_t act, const float* ymask, int32_t ld_ym, float* dgamma,
                                    float* dbeta, int32_t accumulate_param_grads, double* sums, void* ws, size_t ws_bytes, void* stream) {
-  if (num_rows <= 0 || C <= 0 || (C & 3) || C > 1024 || ldx < C || ld_dy < C || ((ldx | ld_dy) & 3) || !sums) return MOPA_ERR_ARG;
-  if (ymask && (ld_ym < C || (ld_ym & 3))) return MOPA_ERR_ARG;
-  if (ws_bytes < mopa_bnrelu_rows_workspace_bytes(num_rows, C)) return MOPA_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = bn_num_blocks(num_rows), RL = 256 / (C >> 2);
-  float* partial = (float*)ws;
+  if (!sums) return MOPA_ERR_ARG;
   BnGroups one;
-  bn_make_groups(&one, num_rows, 1, 0, 0);
-  k_bn_bwd_partial<false><<<nblk, 256, (size_t)2 * RL * C * sizeof(float), st>>>(dy, ld_dy, x, ldx, C, stats, leak, ymask, ld_ym, act, one,
-                                                                                 partial, nullptr);
+  if (int rc = bn_check(&one, num_rows, C, 1, 0, 0, {ldx, ld_dy, ymask ? ld_ym : C}, ws_bytes, mopa_bnrelu_rows_workspace_bytes(num_rows, C)))
+    return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = one.nblk[0], RL = 256 / (C >> 2);
+  float* partial = (float*)ws;
+  k_bn_bwd_partial<<<nblk, 256, (size_t)2 * RL * C * sizeof(float), st>>>(BnRowsMask{dy, ld_dy, ymask, ld_ym}, x, ldx, C, stats, leak, act,
+                                                                         one, partial);
   k_bn_bwd_local_sums<<<C, 256, 0, st>>>(partial, nblk, C, dgamma, dbeta, accumulate_param_grads, sums);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;

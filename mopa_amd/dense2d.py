@@ -28,7 +28,10 @@ LAYERS = [("layer1", 64, 3, 1), ("layer2", 128, 4, 2), ("layer3", 256, 6, 2), ("
 class Img(View):
     """NHWC activation: rows = B*H*W pixels, C channels at column offset `col` of tensor t (ld = t.shape[1])."""
 
-    __slots__ = ("B", "H", "W")
+    # partial / pool: set on a gradient only, by the backward walk.  partial: mopa_colsum's partial sums of it, left by the BatchNorm that wrote
+    # it (a biased convolution's output has that one reader: nothing else adds to the gradient); pool: (dy, argmax, accumulate) of a max-pool
+    # whose backward into it is left to the sums pass of the BatchNorm that reads it
+    __slots__ = ("B", "H", "W", "partial", "pool")
 
     def __init__(self, t, B, H, W, col=0, C=None):
         super().__init__(t, col, C)
@@ -639,24 +642,15 @@ def colsum(x: View, out: torch.Tensor, accumulate=False, partial=None):
 DEFER_BN = os.environ.get("MOPA_DEFER_BN", "1") != "0"
 DEFER_UP_BN = os.environ.get("MOPA_DEFER_UP_BN", "1") != "0"   # ... and the decoder's up-convolution BatchNorms inside the join's consumer
 DEFER_STEM_BN = os.environ.get("MOPA_DEFER_STEM_BN", "1") != "0"   # ... and the stem's inside its two readers (max-pool, full-resolution join)
-# A/B switch: the stem BatchNorm's backward apply inside the stem's weight gradient (mopa_stem_bwd_weight_bn: dx is never written)
-# (the stem's weight gradient with the BatchNorm backward formed in its loader exists as an MFMA kernel only: off with MOPA_CONV2D_MFMA=0)
+# A/B switch: the stem BatchNorm's backward apply inside the stem's weight gradient (mopa_stem_bwd_weight_bn: dx is never written; an MFMA
+# kernel only: off with MOPA_CONV2D_MFMA=0)
 STEM_BN_FUSED_BWD = os.environ.get("MOPA_STEM_BN_FUSED_BWD", "1") != "0" and os.environ.get("MOPA_CONV2D_MFMA", "1") != "0"
-# A/B switch: the second form of that tail (MOPA_STEM_BWD2: 1 = both parts, 0 = neither, "wgrad" / "pool" = one of them).  "pool": the
-# max-pool's backward inside the stem BatchNorm's sums pass (mopa_bn_bwd_sums_groups_pool forms, uses and writes the pooled share of dy:
-# no launch of its own, one pass less over the stem-resolution gradient).  "wgrad": the weight gradient from an image strip in LDS
-# (mopa_stem_bwd_weight_bn2) whose ordered slab reduction writes the parameter gradient's layout.  Same bits as the calls they replace;
-# only where STEM_BN_FUSED_BWD applies (not with want_dimg, a synchronised BatchNorm or MOPA_CONV2D_MFMA=0).
+# A/B switch: the second form of that tail (MOPA_STEM_BWD2: 1 = both parts, 0 = neither, "wgrad" / "pool" = one of them).
+# "pool": the max-pool's backward inside the stem BatchNorm's sums pass (mopa_bn_bwd_sums_groups_pool).  "wgrad": the weight gradient from
+# an image strip in LDS (mopa_stem_bwd_weight_bn2).  Same bits as the calls they replace; only where STEM_BN_FUSED_BWD applies (bn_plan).
 STEM_BWD2 = frozenset({"1": ("wgrad", "pool"), "0": ()}.get(os.environ.get("MOPA_STEM_BWD2", "1"), (os.environ.get("MOPA_STEM_BWD2"),)))
-# (stem pixels B * Hp * Wp from which the second form is dispatched: one 302 x 480 image = 145,920 is inside, as is every training
-# batch; measured at 16 x 304 x 480, profiles/r12_stem_bwd.md.  Below it the tail is a few launches of some microseconds and keeps
-# the first form's calls)
+# (stem pixels B * Hp * Wp from which the second form runs: one 302 x 480 image is inside; profiles/r12_stem_bwd.md)
 STEM_BWD2_MIN_PIXELS = int(os.environ.get("MOPA_STEM_BWD2_MIN_PIXELS", str(1 << 17)))
-
-
-def stem_bwd2(part, B, H, W):
-    """Does `part` ("wgrad" / "pool") of the second form of the stem's backward tail run on a B x H x W stem grid?"""
-    return part in STEM_BWD2 and STEM_BN_FUSED_BWD and B * H * W >= STEM_BWD2_MIN_PIXELS
 # A/B switch: the residual BatchNorms (bn2 of every BasicBlock) leave one bit per element, pre-activation > 0, and their backward pass
 # reads that bit instead of the whole saved output (mopa_bn_act_fwd_groups_bits / mopa_bn_act_bwd_groups_fused)
 BN_MASK_BITS = os.environ.get("MOPA_BN_MASK_BITS", "1") != "0"
@@ -665,48 +659,41 @@ BN_MASK_BITS = os.environ.get("MOPA_BN_MASK_BITS", "1") != "0"
 BN_COLSUM_FUSED = os.environ.get("MOPA_BN_COLSUM_FUSED", "1") != "0"
 
 
+BN_KEYS = (".weight", ".bias", ".running_mean", ".running_var")
+
+
+def _pl(v):   # (pointer, row stride) of an optional View, as the C ABI takes it
+    return (v.p, v.ld) if v is not None else (None, 0)
+
+
+def _bn_tail(query_name, x):   # (workspace, its size, stream): the last three arguments of every BatchNorm entry point
+    ws = workspace.get(query(query_name, x.rows, x.C), x.t.device)
+    return ptr(ws), ws.numel(), stream()
+
+
 def bn_fwd(x: View, y: View, P, name, act, res, training, stats):
     """Returns None, or -- synchronised BatchNorm (mopa_amd.syncbn) in training mode -- the gathered moments for bn_bwd."""
     if training and syncbn.active():
-        return syncbn.fwd(x, y, P[name + ".weight"], P[name + ".bias"], P[name + ".running_mean"], P[name + ".running_var"],
-                          BN_MOMENTUM, BN_EPS, 0.0, act, res, stats)
-    wsb = query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C)
-    ws = workspace.get(wsb, x.t.device)
-    call("mopa_bn_act_fwd", x.p, x.ld, y.p, y.ld, x.rows, x.C, ptr(P[name + ".weight"]), ptr(P[name + ".bias"]),
-         ptr(P[name + ".running_mean"]), ptr(P[name + ".running_var"]), BN_MOMENTUM, BN_EPS, 0.0, int(act),
-         res.p if res is not None else None, res.ld if res is not None else 0, int(training), ptr(stats), ptr(ws),
-         ws.numel(), stream())
+        return syncbn.fwd(x, y, *(P[name + k] for k in BN_KEYS), BN_MOMENTUM, BN_EPS, 0.0, act, res, stats)
+    call("mopa_bn_act_fwd", x.p, x.ld, y.p, y.ld, x.rows, x.C, *(ptr(P[name + k]) for k in BN_KEYS), BN_MOMENTUM, BN_EPS, 0.0, int(act),
+         *_pl(res), int(training), ptr(stats), *_bn_tail("mopa_bnrelu_rows_workspace_bytes", x))
 
 
 def bn_fwd_groups(x: View, y: View | None, P, name, act, res, training, stats, G, bits=None):
-    """bn_fwd for G consecutive, equally sized row groups of one tensor in ONE set of launches (3 instead of 3 G): statistics, running
-    updates (group 0 first) and the apply per group, bit-identical to G calls of bn_fwd on the row ranges.  stats: (G, 4, C).
-    y = None: no apply pass (the consumer applies stats while it reads x: LazyImg).
-    bits: (rows, C / 32) int32 that receives the activation bits of a residual layer for bn_bwd_fused."""
+    """bn_fwd for G consecutive, equally sized row groups of one tensor in ONE set of launches (3 instead of 3 G), bit-identical to G calls of
+    bn_fwd on the row ranges (running updates: group 0 first).  stats: (G, 4, C).  y = None: no apply pass (the consumer applies stats while
+    it reads x: LazyImg).  bits: (rows, C / 32) int32 that receives the activation bits of a residual layer for bn_bwd_fused."""
     n = x.rows // G
-    wsb = query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C)
-    ws = workspace.get(wsb, x.t.device)
-    if bits is not None:
-        call("mopa_bn_act_fwd_groups_bits", x.p, x.ld, y.p, y.ld, x.rows, x.C, G, n, 2 * n,
-             ptr(P[name + ".weight"]), ptr(P[name + ".bias"]),
-             ptr(P[name + ".running_mean"]), ptr(P[name + ".running_var"]), BN_MOMENTUM, BN_EPS, 0.0, int(act),
-             res.p, res.ld, int(training), ptr(stats), 1, ptr(bits), ptr(ws), ws.numel(), stream())
-        return
-    call("mopa_bn_act_fwd_groups", x.p, x.ld, y.p if y is not None else None, y.ld if y is not None else 0, x.rows, x.C, G, n, 2 * n,
-         ptr(P[name + ".weight"]), ptr(P[name + ".bias"]),
-         ptr(P[name + ".running_mean"]), ptr(P[name + ".running_var"]), BN_MOMENTUM, BN_EPS, 0.0, int(act),
-         res.p if res is not None else None, res.ld if res is not None else 0, int(training), ptr(stats), ptr(ws),
-         ws.numel(), stream())
+    call("mopa_bn_act_fwd_groups" + ("_bits" if bits is not None else ""), x.p, x.ld, *_pl(y), x.rows, x.C, G, n, 2 * n,
+         *(ptr(P[name + k]) for k in BN_KEYS), BN_MOMENTUM, BN_EPS, 0.0, int(act), *_pl(res), int(training), ptr(stats),
+         *((1, ptr(bits)) if bits is not None else ()), *_bn_tail("mopa_bnrelu_rows_workspace_bytes", x))
 
 
 def bn_bwd_groups(dy: View, x: View, dx: View, stats, act, ymask, dres, acc_dres, training, dgamma, dbeta, G, acc_params=False):
     n = x.rows // G
-    wsb = query("mopa_bnrelu_rows_bwd_workspace_bytes", x.rows, x.C)
-    ws = workspace.get(wsb, x.t.device)
-    call("mopa_bn_act_bwd_groups", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act),
-         ymask.p if ymask is not None else None, ymask.ld if ymask is not None else 0,
-         dres.p if dres is not None else None, dres.ld if dres is not None else 0, int(acc_dres), int(training),
-         ptr(dgamma), ptr(dbeta), int(acc_params), 0, ptr(ws), ws.numel(), stream())
+    call("mopa_bn_act_bwd_groups", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act), *_pl(ymask),
+         *_pl(dres), int(acc_dres), int(training), ptr(dgamma), ptr(dbeta), int(acc_params), 0,
+         *_bn_tail("mopa_bnrelu_rows_bwd_workspace_bytes", x))
 
 
 def bn_bwd_fused(dy: View, x: View, dx: View, stats, act, bits, dres, acc_dres, training, dgamma, dbeta, G, acc_params=False,
@@ -714,14 +701,10 @@ def bn_bwd_fused(dy: View, x: View, dx: View, stats, act, bits, dres, acc_dres, 
     """bn_bwd_groups with the activation mask from `bits` (bn_fwd_groups; None: recomputed from x) and, want_colsum, -> mopa_colsum's
     partial sums of the dx it writes, a tensor of their own (the shared workspace is re-used by the kernels that follow)."""
     n = x.rows // G
-    wsb = query("mopa_bn_act_bwd_groups_fused_workspace_bytes", x.rows, x.C)
-    ws = workspace.get(wsb, x.t.device)
-    partial = None
-    if want_colsum:
-        partial = torch.empty(query("mopa_colsum_partial_blocks", x.rows) * x.C, dtype=torch.float32, device=x.t.device)
+    partial = torch.empty(query("mopa_colsum_partial_blocks", x.rows) * x.C, dtype=torch.float32, device=x.t.device) if want_colsum else None
     call("mopa_bn_act_bwd_groups_fused", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act),
-         int(bits is not None), ptr(bits), dres.p if dres is not None else None, dres.ld if dres is not None else 0, int(acc_dres),
-         int(training), ptr(dgamma), ptr(dbeta), int(acc_params), 0, ptr(partial), ptr(ws), ws.numel(), stream())
+         int(bits is not None), ptr(bits), *_pl(dres), int(acc_dres), int(training), ptr(dgamma), ptr(dbeta), int(acc_params), 0,
+         ptr(partial), *_bn_tail("mopa_bn_act_bwd_groups_fused_workspace_bytes", x))
     return partial
 
 
@@ -729,18 +712,112 @@ def bn_bwd(dy: View, x: View, dx: View, stats, act, ymask, dres, acc_dres, train
            acc_params=False, gathered=None):
     if gathered is not None:   # the forward pass of this layer ran with global statistics
         return syncbn.bwd(dy, x, dx, stats, 0.0, act, ymask, dres, acc_dres, dgamma, dbeta, acc_params, acc_dx, gathered)
-    wsb = query("mopa_bnrelu_rows_bwd_workspace_bytes", x.rows, x.C)
-    ws = workspace.get(wsb, x.t.device)
-    call("mopa_bn_act_bwd", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, ptr(stats), 0.0, int(act),
-         ymask.p if ymask is not None else None, ymask.ld if ymask is not None else 0,
-         dres.p if dres is not None else None, dres.ld if dres is not None else 0, int(acc_dres), int(training),
-         ptr(dgamma), ptr(dbeta), int(acc_params), int(acc_dx), ptr(ws), ws.numel(), stream())
+    call("mopa_bn_act_bwd", dy.p, dy.ld, x.p, x.ld, dx.p, dx.ld, x.rows, x.C, ptr(stats), 0.0, int(act), *_pl(ymask), *_pl(dres),
+         int(acc_dres), int(training), ptr(dgamma), ptr(dbeta), int(acc_params), int(acc_dx), *_bn_tail("mopa_bnrelu_rows_bwd_workspace_bytes", x))
+
+
+def bn_bwd_sums(dy: View, x: Img, stats, act, dgamma, dbeta, G, acc_params=False, pool=None):
+    """The sums pass alone -> coef (G, 2, C), for a reader that applies the BatchNorm backward while it reads (dy, x): the stem's weight
+    gradient.  pool = (dpool, argmax, accumulate): a max-pool's backward into dy that is still to run; the pass forms, uses and writes it."""
+    n, coef = x.rows // G, torch.empty(G, 2, x.C, dtype=torch.float32, device=x.t.device)
+    head = (dy.p, dy.ld, x.p, x.ld, x.rows, x.C, G, n, 2 * n) if pool is None else \
+        (pool[0].p, pool[0].ld, ptr(pool[1]), x.B, x.H, x.W, dy.p, dy.ld, int(pool[2]), x.p, x.ld, x.C, G)
+    call("mopa_bn_bwd_sums_groups" + ("" if pool is None else "_pool"), *head, ptr(stats), 0.0, int(act), *((None, 0) if pool is None else ()),
+         ptr(dgamma), ptr(dbeta), int(acc_params), ptr(coef), *_bn_tail("mopa_bnrelu_rows_workspace_bytes", x))
+    return coef
+
+
+class BnPlan(NamedTuple):
+    """What a BatchNorm layer of the backbone runs as in each pass, named after the forms."""
+    fwd: str            # "stats" (no apply pass: LazyImg), "groups_bits", "groups", "single" (per group), "sync" (per group, mopa_amd.syncbn)
+    bwd: str            # "sums_pool", "sums" (no apply pass: the stem's weight gradient applies), "fused", "groups", "single", "sync"
+    bits: bool          # the forward pass leaves the activation bits and the backward pass reads them instead of the saved output
+    colsum: bool        # the backward apply pass leaves the partial column sums of its dx (the producer's bias gradient)
+    pool_inside: bool   # the backward of the max-pool that reads this layer is left to this layer's sums pass
+    stem_wgrad: str     # the stem's weight gradient behind this layer: "strip" / "im2col_bn" (they apply this layer's backward), "plain"
+
+
+def bn_plan(C, G, training, keep_tape, act, res, deferred, sync, biased=False, stem=False, pool_reader=False, grid=(0, 0, 0),
+            want_dimg=False, bits=None) -> BnPlan:
+    """The one place where a BatchNorm layer's forms are chosen; pure, not cached: the switches are read at every call.
+    deferred: the output is a LazyImg; sync: mopa_amd.syncbn is active; biased: the producer is a convolution with a bias; stem: the stem's
+    bn1, grid its B, H, W; pool_reader: a max-pool reads the output; bits: None = the forward half decides, else what the tape holds."""
+    synced = bool(training and sync and not deferred)   # (a deferred layer has no synchronised form: its callers do not defer under one)
+    second = lambda part: part in STEM_BWD2 and STEM_BN_FUSED_BWD and grid[0] * grid[1] * grid[2] >= STEM_BWD2_MIN_PIXELS   # noqa: E731
+    if bits is None:
+        bits = bool(BN_MASK_BITS and not deferred and keep_tape and training and res and act == 1 and C % 32 == 0 and not sync)
+    fwd = ("stats" if deferred else "groups_bits" if bits else "groups" if G > 1 and not (training and sync) else "sync" if synced else "single")
+    sums = bool(STEM_BN_FUSED_BWD and stem and C == 64 and not want_dimg and not res and act == 1 and not synced)
+    pool_inside = bool(sums and pool_reader and deferred and second("pool"))
+    # (the fused entry point has no ymask: a residual layer without bits keeps the path that reads the saved output)
+    fusable = not synced and (not res or bits)
+    colsum = bool(not sums and fusable and biased and BN_COLSUM_FUSED)
+    bwd = (("sums_pool" if pool_inside else "sums") if sums else "sync" if synced else "fused" if fusable and (bits or colsum)
+           else "groups" if G > 1 else "single")
+    return BnPlan(fwd, bwd, bool(bits), colsum, pool_inside, "plain" if not sums else "strip" if second("wgrad") else "im2col_bn")
+
+
+# What the stem's BatchNorm hands to the stem's weight gradient when it ran its sums pass only (BnPlan.stem_wgrad != "plain"): dy is the
+# gradient of the BatchNorm's OUTPUT; the weight gradient's loader applies the rest from x, stats (G, 4, C) and coef (G, 2, C)
+StemGrad = NamedTuple("StemGrad", [("dy", Img), ("x", Img), ("stats", torch.Tensor), ("coef", torch.Tensor)])
+
+
+class BnOp:
+    """BatchNorm2d (+ residual) (+ ReLU) over G consecutive row groups, the counterpart of ConvOp: bn_plan chooses, this makes the calls.
+    One per layer and pass: forward() leaves what backward() reads on the op.  stem_grid = (B, H, W): this is the stem's bn1."""
+
+    def __init__(self, P, name, act=1, res=None, G=1, biased=False, stem_grid=None):
+        self.P, self.name, self.act, self.res, self.G, self.biased, self.stem_grid = P, name, act, res, G, biased, stem_grid
+        self.x = self.y = self.stats = self.gathered = self.bits = None
+
+    def plan(self, training, want_dimg=False, C=None, keep_tape=True, deferred=False) -> BnPlan:
+        """Before the forward pass, from C, keep_tape and deferred; after it, from the switches as they are now and what it left."""
+        ran, stem = self.x is not None, self.stem_grid is not None   # (the max-pool reads the stem's BatchNorm and no other)
+        return bn_plan(self.x.C if ran else C, self.G, training, keep_tape, self.act, self.res is not None, hasattr(self.y, "bn") if ran else deferred,
+                       self.gathered is not None if ran else syncbn.active(), self.biased, stem, stem, self.stem_grid or (0, 0, 0), want_dimg,
+                       self.bits is not None if ran else None)
+
+    def forward(self, x: Img, out, training, keep_tape=True, defer=False):
+        """-> y; defer: statistics only, y is a LazyImg and its consumer applies them while it reads x."""
+        G, P, name, res = self.G, self.P, self.name, self.res
+        plan = self.plan(training, C=x.C, keep_tape=keep_tape, deferred=defer)
+        assert plan.fwd != "stats" or (self.act == 1 and res is None and out is None)
+        stats = torch.empty(G, 4, x.C, dtype=torch.float32, device=x.t.device)
+        y = None if plan.fwd == "stats" else out if out is not None else new_img(x.B, x.H, x.W, x.C, x.t.device)
+        self.bits = torch.empty(x.rows, x.C // 32, dtype=torch.int32, device=x.t.device) if plan.bits else None   # (the ReLU mask, 1 bit per element)
+        if plan.fwd in ("single", "sync"):
+            got = [bn_fwd(_group(x, g, G), _group(y, g, G), P, name, self.act, _group(res, g, G), training, stats[g]) for g in range(G)]
+            self.gathered = got if plan.fwd == "sync" else None
+        else:   # one set of launches for all groups
+            bn_fwd_groups(x, y, P, name, self.act, res, training, stats, G, self.bits)
+        self.x, self.stats, self.y = x, stats, LazyImg(x, stats, G) if y is None else y
+        return self.y
+
+    def backward(self, dy: Img, dres, acc_dres, training, dgamma, dbeta, acc_params, want_dimg):
+        """-> the gradient of the BatchNorm's input: an Img (with .partial where the plan says colsum) or, the sums forms, a StemGrad."""
+        x, stats, G, act = self.x, self.stats, self.G, self.act
+        plan = self.plan(training, want_dimg)
+        pool = getattr(dy, "pool", None)
+        assert (pool is not None) == plan.pool_inside
+        if plan.stem_wgrad != "plain":   # sums + parameter gradients here, no apply pass, no dx tensor
+            return StemGrad(dy, x, stats, bn_bwd_sums(dy, x, stats, act, dgamma, dbeta, G, acc_params, pool))
+        dx = new_img(x.B, x.H, x.W, x.C, x.t.device)
+        ymask = self.y if self.res is not None else None
+        if plan.bwd == "fused":
+            dx.partial = bn_bwd_fused(dy, x, dx, stats, act, self.bits, dres, acc_dres, training, dgamma, dbeta, G, acc_params, plan.colsum)
+        elif plan.bwd == "groups":
+            bn_bwd_groups(dy, x, dx, stats, act, ymask, dres, acc_dres, training, dgamma, dbeta, G, acc_params)
+        else:
+            for g in range(G):
+                bn_bwd(_group(dy, g, G), _group(x, g, G), _group(dx, g, G), stats[g], act, _group(ymask, g, G), _group(dres, g, G), acc_dres,
+                       training, dgamma, dbeta, acc_params=acc_params or g > 0, gathered=None if self.gathered is None else self.gathered[g])
+        return dx
 
 
 # ------------------------------------------------------------------------------------------------ the backbone passes
 def _group(v: Img, g, G):
-    """The g-th of G equal image groups of an NHWC activation (a row range of the same buffer)."""
-    if G == 1:
+    """The g-th of G equal image groups of an NHWC activation (a row range of the same buffer); None stays None."""
+    if G == 1 or v is None:
         return v
     n = v.rows // G
     return Img(v.t[g * n:(g + 1) * n], v.B // G, v.H, v.W, v.col, v.C)
@@ -773,30 +850,12 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
     tape = [] if keep_tape else _NoTape()
     nbt = []   # BatchNorm2d.num_batches_tracked of every layer that ran: bumped together at the end (one launch, not 43)
 
-    def bn(name, x, act=1, res=None, out=None, defer=False):
-        stats = torch.empty(G, 4, x.C, dtype=torch.float32, device=dev)
-        if defer:   # statistics only; the next convolution's input transform applies them
-            assert act == 1 and res is None and out is None
-            bn_fwd_groups(x, None, P, name, act, None, training, stats, G)
-            y = LazyImg(x, stats, G)
-            if training:
-                nbt.append(P[name + ".num_batches_tracked"])
-            tape.append(("bn", name, x, y, stats, act, None, [None] * G, None))
-            return y
-        y = out if out is not None else new_img(x.B, x.H, x.W, x.C, dev)
-        bits = None
-        if BN_MASK_BITS and keep_tape and training and res is not None and act == 1 and x.C % 32 == 0 and not syncbn.active():
-            bits = torch.empty(x.rows, x.C // 32, dtype=torch.int32, device=dev)   # the ReLU mask for the backward pass, 1 bit per element
-        if bits is not None or (G > 1 and not (training and syncbn.active())):
-            bn_fwd_groups(x, y, P, name, act, res, training, stats, G, bits)     # one set of launches for all groups
-            gathered = [None] * G
-        else:
-            gathered = [bn_fwd(_group(x, g, G), _group(y, g, G), P, name, act, None if res is None else _group(res, g, G), training,
-                               stats[g]) for g in range(G)]
+    def bn(name, x, act=1, res=None, out=None, defer=False, **layer):
+        op = layer["op"] if "op" in layer else BnOp(P, name, act, res, G, **layer)
         if training:
             nbt.append(P[name + ".num_batches_tracked"])
-        tape.append(("bn", name, x, y, stats, act, res, gathered, bits))
-        return y
+        tape.append(("bn", op))
+        return op.forward(x, out, training, keep_tape, defer)
 
     def takes_lazy(name, B, H, W):   # may this 3x3 convolution's input be a LazyImg?
         cout, cin = P[name + ".weight"].shape[:2]
@@ -842,17 +901,17 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
     stem_g = _geom(B=B, IH=Hp + 6, IW=Wp + 8, OHl=Hp, OWl=Wp, OHa=Hp, OWa=Wp, IDX=4, TH=7, TW=2, KWF=2, Cin=16,
                    Cout=64, ld_in=4, ld_out=c1.ld)
     igemm(ptr(x4), w1, None, c1.p, stem_g)
-    tape.append(("stem", x4, c1, stem_g))
+    bn1 = BnOp(P, pre + "bn1", G=G, stem_grid=(B, Hp, Wp))   # (the stem's and the max-pool's backward ask this layer's plan)
+    tape.append(("stem", x4, c1, stem_g, bn1))
     H2, W2 = Hp // 2, Wp // 2
     x = new_img(B, H2, W2, 64, dev)
     amax = torch.empty(B * H2 * W2 * 64, dtype=torch.uint8, device=dev)
+    skip0 = bn(pre + "bn1", c1, out=None if lazy_stem else Img(J[0], B, Hp, Wp, 0, 64), defer=lazy_stem, op=bn1)
     if lazy_stem:
-        skip0 = bn(pre + "bn1", c1, defer=True)
         call("mopa_maxpool3x3s2_fwd_bn", c1.p, c1.ld, B, Hp, Wp, 64, ptr(skip0.bn[0]), G, x.p, x.ld, ptr(amax), stream())
     else:
-        skip0 = bn(pre + "bn1", c1, out=Img(J[0], B, Hp, Wp, 0, 64))
         call("mopa_maxpool3x3s2_fwd", skip0.p, skip0.ld, B, Hp, Wp, 64, x.p, x.ld, ptr(amax), stream())
-    tape.append(("maxpool", skip0, x, amax))
+    tape.append(("maxpool", skip0, x, amax, bn1))
     # ---- encoder stages
     for li, (lname, c, nblocks, stride) in enumerate(LAYERS):
         for b in range(nblocks):
@@ -871,7 +930,6 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
                 lvl = li + 1
                 J[lvl] = torch.empty(z.rows, 2 * c, dtype=torch.float32, device=dev)
                 out = Img(J[lvl], z.B, z.H, z.W, 0, c)
-            tape.append(("block_in", x))
             x = bn(q + "bn2", z, act=1, res=idt, out=out)
         if lname == "layer3":   # dropout, then the result is skip3 AND layer4's input (:153-155)
             J[3] = torch.empty(x.rows, 2 * c, dtype=torch.float32, device=dev)
@@ -892,7 +950,7 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
         if lazy_up:
             right = Img(J[lvl], x.B, 2 * x.H, 2 * x.W, cj, cj)
             up_raw = convT(tname + "0", x, out=right)
-            ylazy = bn(tname + "1", up_raw, defer=True)
+            ylazy = bn(tname + "1", up_raw, defer=True, biased=True)
             if lvl == 0 and lazy_stem:   # both halves are raw: [stem conv | up-convolution], one statistics tensor over the 128 channels
                 st2 = torch.empty(G, 4, 2 * cj, dtype=torch.float32, device=dev)   # [stem | up-convolution] statistics side by side
                 for half, src in enumerate((skip0.bn[0], ylazy.bn[0])):
@@ -902,13 +960,13 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
                 joined = LazyImg(Img(J[lvl], up_raw.B, up_raw.H, up_raw.W, 0, 2 * cj), ylazy.bn[0], G, c0=cj)
         else:
             up_raw = convT(tname + "0", x)
-            bn(tname + "1", up_raw, out=Img(J[lvl], up_raw.B, up_raw.H, up_raw.W, cj, cj))
+            bn(tname + "1", up_raw, out=Img(J[lvl], up_raw.B, up_raw.H, up_raw.W, cj, cj), biased=True)
             joined = Img(J[lvl], up_raw.B, up_raw.H, up_raw.W, 0, 2 * cj)
         tape.append(("join", lvl, cj, lazy_up, lvl == 0 and lazy_stem))
         if lvl == 0:
             x = conv(pre + "dec_conv_stage1", joined, 3, 1, 1, bias=True)
         else:
-            x = bn(cname[:-1] + "1", conv(cname, joined, 3, 1, 1, bias=True))
+            x = bn(cname[:-1] + "1", conv(cname, joined, 3, 1, 1, bias=True), biased=True)
     for i in range(0, len(nbt), 64):   # one launch per 64 counters (43 BatchNorm layers: one)
         tab = np.zeros(64, np.int64)
         tab[:len(nbt[i:i + 64])] = [t.data_ptr() for t in nbt[i:i + 64]]
@@ -942,88 +1000,39 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
     def like(v: Img, zero=False):
         return new_img(v.B, v.H, v.W, v.C, dev, zero=zero)
 
+    def grad_of(v):   # -> (the gradient tensor of v, does it hold a reader's share already?)
+        k = key(v)
+        acc = k in gmap
+        gmap[k] = gmap[k] if acc else like(v)
+        return gmap[k], acc
+
     gmap[key(feat)] = dfeat
-    dJ = {}  # gradient buffers of the join tensors (full width)
-    # outputs of the convolutions with a bias: a BatchNorm that reads one leaves the partial column sums of its dx for the bias gradient
-    biased = {key(r[4]) for r in tape if r[0] in ("conv", "convT") and r[2].b is not None} if BN_COLSUM_FUSED else set()
-    db_partials = {}
-    pool_deferred = {}   # key of a max-pool's input -> (dy, argmax, accumulate): its backward runs inside the next BatchNorm backward
     for rec in reversed(tape):
         kind = rec[0]
         if kind == "bn":
-            _, name, x, y, stats, act, res, gathered, bits = rec
-            dy = gmap.pop(key(y))
-            dres = None
-            acc_dres = False
-            if res is not None:
-                k = key(res)
-                if k in gmap:
-                    dres, acc_dres = gmap[k], True
-                else:
-                    dres = like(res)
-                    gmap[k] = dres
-            (dg, db), pacc = sink.take(name + ".weight", name + ".bias")
-            pool = pool_deferred.pop(key(y), None)   # (the max-pool's backward into dy is still to run: see "maxpool" below)
-            stem_fused = (STEM_BN_FUSED_BWD and name == pre + "bn1" and not want_dimg and res is None and act == 1
-                          and all(gt is None for gt in gathered) and x.C == 64)
-            if pool is not None and not stem_fused:
-                pdy, amax, pacc_dy = pool
-                call("mopa_maxpool3x3s2_bwd", pdy.p, pdy.ld, ptr(amax), x.B, x.H, x.W, x.C, dy.p, dy.ld, int(pacc_dy), stream())
-                pool = None
-            if stem_fused:
-                # the stem's BatchNorm: its input gradient has ONE reader, the stem's weight gradient, which forms it from (dy, x)
-                # itself -- sums + parameter gradients here, no apply pass, no dx tensor
-                n = x.rows // G
-                coef = torch.empty(G, 2, x.C, dtype=torch.float32, device=dev)
-                ws = workspace.get(query("mopa_bnrelu_rows_workspace_bytes", x.rows, x.C), dev)
-                if pool is not None:   # ... and the sums pass forms the max-pool's share of dy on its way
-                    pdy, amax, pacc_dy = pool
-                    call("mopa_bn_bwd_sums_groups_pool", pdy.p, pdy.ld, ptr(amax), x.B, x.H, x.W, dy.p, dy.ld, int(pacc_dy), x.p, x.ld,
-                         x.C, G, ptr(stats), 0.0, int(act), ptr(dg), ptr(db), int(pacc), ptr(coef), ptr(ws), ws.numel(), stream())
-                else:
-                    call("mopa_bn_bwd_sums_groups", dy.p, dy.ld, x.p, x.ld, x.rows, x.C, G, n, 2 * n, ptr(stats), 0.0, int(act), None, 0,
-                         ptr(dg), ptr(db), int(pacc), ptr(coef), ptr(ws), ws.numel(), stream())
-                gmap[key(x)] = ("bn", dy, x, stats, coef)
-                continue
-            dx = like(x)
-            gmap[key(x)] = dx
-            local = all(gt is None for gt in gathered)   # (not synchronised)
-            # (the fused entry point has no ymask: a residual layer without bits keeps the path that reads the saved output)
-            fusable = local and (res is None or bits is not None)
-            want_colsum = fusable and key(x) in biased
-            if fusable and (bits is not None or want_colsum):
-                part = bn_bwd_fused(dy, x, dx, stats, act, bits, dres, acc_dres, training, dg, db, G, acc_params=pacc, want_colsum=want_colsum)
-                if want_colsum:
-                    db_partials[key(x)] = part
-            elif G > 1 and local:
-                bn_bwd_groups(dy, x, dx, stats, act, y if res is not None else None, dres, acc_dres, training, dg, db, G, acc_params=pacc)
-            else:
-                for g in range(G):
-                    bn_bwd(_group(dy, g, G), _group(x, g, G), _group(dx, g, G), stats[g], act,
-                           _group(y, g, G) if res is not None else None, None if dres is None else _group(dres, g, G), acc_dres, training,
-                           dg, db, acc_params=pacc or g > 0, gathered=gathered[g])
+            op = rec[1]
+            dy = gmap.pop(key(op.y))
+            dres, acc_dres = grad_of(op.res) if op.res is not None else (None, False)
+            (dg, db), pacc = sink.take(op.name + ".weight", op.name + ".bias")
+            gmap[key(op.x)] = op.backward(dy, dres, acc_dres, training, dg, db, pacc, want_dimg)
         elif kind == "conv":
             _, name, op, x, out, V = rec
             dout = gmap.pop(key(out))
-            k = key(x)
-            acc = k in gmap
-            dx = gmap[k] if acc else like(x)
-            gmap[k] = dx
+            dx, acc = grad_of(x)
             pg, pacc = sink.take(*([name + ".weight"] + ([name + ".bias"] if op.b is not None else [])))
             op.backward(x, dout, dx, pg[0], pg[1] if op.b is not None else None, acc, acc_params=pacc, V=V, wgrad_side=True,
-                        db_partial=db_partials.pop(key(out), None))
+                        db_partial=getattr(dout, "partial", None))
         elif kind == "convT":
             _, name, op, x, out = rec
             dout = gmap.pop(key(out))
             dx = like(x)
             gmap[key(x)] = dx
             (dw, db), pacc = sink.take(name + ".weight", name + ".bias")
-            op.backward(x, dout, dx, dw, db, acc_params=pacc, wgrad_side=True, db_partial=db_partials.pop(key(out), None))
+            op.backward(x, dout, dx, dw, db, acc_params=pacc, wgrad_side=True, db_partial=getattr(dout, "partial", None))
         elif kind == "join":
             _, lvl, cj, lazy_up, lazy_left = rec
             lz = (1,) if lazy_up else ()   # (the join was consumed as a LazyImg: see key())
             full = gmap.pop((J[lvl].data_ptr(), 0, 2 * cj) + lz)
-            dJ[lvl] = full
             if DEBUG is not None:
                 DEBUG[f"dJ{lvl}"] = full.t.clone()
             gmap[(J[lvl].data_ptr(), 0, cj) + ((1,) if lazy_left else ())] = Img(full.t, full.B, full.H, full.W, 0, cj)
@@ -1036,47 +1045,36 @@ def _backbone_backward(P, sink, tape, J, feat, dfeat, training, drop_seed, seed_
             for g in range(G):
                 dropout_rows(_group(dy, g, G), _group(dx, g, G), p, seeds[g], None if seed_t is None else seed_t[g:], site)
         elif kind == "maxpool":
-            _, x, y, amax = rec
+            _, x, y, amax, bn1 = rec
             dy = gmap.pop(key(y))
-            k = key(x)
-            acc = k in gmap
-            dx = gmap[k] if acc else like(x)
-            gmap[k] = dx
-            if stem_bwd2("pool", x.B, x.H, x.W) and not want_dimg and hasattr(x, "bn"):
+            dx, acc = grad_of(x)
+            if bn1.plan(training, want_dimg).pool_inside:
                 # the pool input is the stem's deferred BatchNorm, whose backward comes next and reads every element of dx: left to it
-                pool_deferred[k] = (dy, amax, acc)
+                dx.pool = (dy, amax, acc)
             else:
                 call("mopa_maxpool3x3s2_bwd", dy.p, dy.ld, ptr(amax), x.B, x.H, x.W, x.C, dx.p, dx.ld, int(acc), stream())
         elif kind == "stem":
-            _, x4, c1, g = rec
-            dout = gmap.pop(key(c1))
+            _, x4, c1, g, bn1 = rec
+            dout = gmap.pop(key(c1))   # (a StemGrad unless the weight gradient is the plain one)
+            wg = bn1.plan(training, want_dimg).stem_wgrad
             (dw,), pacc = sink.take(pre + "conv1.weight")
-            lazy = dout if isinstance(dout, tuple) else None   # ("bn", dy, x, stats, coef): the BatchNorm above left its apply to us
             # (the weight-gradient stream reads dy and, fused, the small coef tensor: both are dropped here before the streams are joined)
-            with _on(wgrad_stream(dev), (lazy[1] if lazy else dout).t, *((lazy[4],) if lazy else ())):
-                if lazy and stem_bwd2("wgrad", B, Hp, Wp):   # the strip kernel; its slab reduction writes dw itself (flags bit 1)
-                    _, bdy, bx, bstats, bcoef = lazy
+            with _on(wgrad_stream(dev), *((dout.t,) if wg == "plain" else (dout.dy.t, dout.coef))):
+                dwl = None if wg == "strip" else torch.empty(7, 2, 16, 64, dtype=torch.float32, device=dev)
+                if wg == "plain":
+                    if g[24] != dout.ld:   # (forward wrote into a wider buffer; the gradient tensor has its own row stride)
+                        g = (ctypes.c_int32 * 25)(*g[:24], dout.ld)
+                    wgrad(ptr(x4), dout.p, ptr(dwl), g, dev)
+                else:   # the BatchNorm above left its apply to us; "strip": the slab reduction writes dw itself (flags bit 1)
                     ws = workspace.get(query("mopa_conv2d_wgrad_workspace_bytes", ctypes.addressof(g)), dev)
-                    call("mopa_stem_bwd_weight_bn2", ptr(x4), bdy.p, bdy.ld, bx.p, bx.ld, ptr(bstats), ptr(bcoef), G, int(training), ptr(dw),
-                         ctypes.addressof(g), int(pacc) | 2, ptr(ws), ws.numel(), stream())
-                else:
-                    dwl = torch.empty(7, 2, 16, 64, dtype=torch.float32, device=dev)
-                    if lazy:
-                        _, bdy, bx, bstats, bcoef = lazy
-                        ws = workspace.get(query("mopa_conv2d_wgrad_workspace_bytes", ctypes.addressof(g)), dev)
-                        call("mopa_stem_bwd_weight_bn", ptr(x4), bdy.p, bdy.ld, bx.p, bx.ld, ptr(bstats), ptr(bcoef), G, int(training), ptr(dwl),
-                             ctypes.addressof(g), 0, ptr(ws), ws.numel(), stream())
-                    else:
-                        if g[24] != dout.ld:   # (forward wrote into a wider buffer; the gradient tensor has its own row stride)
-                            g = (ctypes.c_int32 * 25)(*g)
-                            g[24] = dout.ld
-                        wgrad(ptr(x4), dout.p, ptr(dwl), g, dev)
+                    call("mopa_stem_bwd_weight_bn" + ("2" if wg == "strip" else ""), ptr(x4), dout.dy.p, dout.dy.ld, dout.x.p, dout.x.ld,
+                         ptr(dout.stats), ptr(dout.coef), G, int(training), ptr(dwl if dwl is not None else dw), ctypes.addressof(g),
+                         (int(pacc) | 2) if wg == "strip" else 0, ptr(ws), ws.numel(), stream())
+                if dwl is not None:
                     call("mopa_conv2d_stem_relayout", ptr(dwl), ptr(dw), 64, 1, int(pacc), stream())
             if want_dimg:   # gradient w.r.t. the image itself (not asked for by MoPA's training)
                 dimg = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
                 call("mopa_stem_dgrad_image", dout.p, dout.ld, B, Hp, Wp, H, W, ptr(P[pre + "conv1.weight"]), ptr(dimg), stream())
-        elif kind == "block_in":
-            pass
     join_wgrad_stream(dev)   # the weight gradients are complete for whatever the caller queues next
     return dimg
 

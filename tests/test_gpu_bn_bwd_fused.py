@@ -22,6 +22,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS, MOM = 1e-5, 0.1
 PAD, COL = 16, 8   # x, dy and dx are column slices [COL, COL + C) of buffers C + PAD wide
+TOL, TOL_DRES = (1e-3, 1e-4), (1e-4, 2e-5)   # (rtol, atol of the tensor's scale) against the fp64 formula; tests/test_gpu_bn_plan.py uses them too
 
 
 def _close(got, ref, rtol, atol):
@@ -183,10 +184,10 @@ def test_mask_bits_and_fused_column_sums_give_the_bits_of_the_existing_kernels(r
     # fp64: the fused forms against the formula (mask = the stored output's sign, the exact zeros have no sign in fp64)
     dx, dres, dg, db, part = c.bwd(dres0, 0, bits=bits, colsum=True)
     rdx, rdz, rdg, rdb = c.reference(c.y > 0)
-    _close(dx.v, rdx, 1e-3, 1e-4)
-    _close(dres, rdz, 1e-4, 2e-5)
-    _close(dg - 0.25, rdg, 1e-3, 1e-4)
-    _close(db + 0.5, rdb, 1e-3, 1e-4)
+    _close(dx.v, rdx, *TOL)
+    _close(dres, rdz, *TOL_DRES)
+    _close(dg - 0.25, rdg, *TOL)
+    _close(db + 0.5, rdb, *TOL)
     bias = torch.zeros(C, device="cuda")
     c.call("mopa_colsum_reduce", part.data_ptr(), rows, C, bias.data_ptr(), 0, c.stream())
     # The column sums: the exact sum of a BatchNorm's dx over a group is 0, so the yardstick is the fp64 sum of the dx that was written,
