@@ -157,6 +157,261 @@ MOPA_API int mopa_wce_bwd(const float* logits, const int64_t* labels, const floa
   return MOPA_OK;
 }
 
+// ------------------------------------------------------------------------------------------ per-point training losses
+// The loss-and-metric block between the forward and backward passes of one domain half (train_xmuda_mopa.py:353-418,
+// :437-469,:563-576) in ONE row pass over the per-point logits of both networks: the two weighted CE values, the two
+// cross-modal KL values, SegIoU's two confusion matrices and pc_mm_acc's two counts.  Partition, accumulation order and the
+// CE / KL expressions are those of k_wce_partial / k_kl_partial / k_wce_finalize / k_scalar_finalize above, so every scalar
+// has the bits of the single entry point; the integers go through per-block LDS counters flushed with integer atomics, like
+// k_eval_logits (evaluate.hip).  The backward is one launch per network, as the reference backpropagates the two networks'
+// loss sums separately.
+#define PL_NPART 6   // per-block partials: CE numerator, CE normaliser, KL sum of the 2D network, then of the 3D network
+#define PL_MAXGRID 2048
+
+struct PointLossArgs {
+  const float* zm[2];        // (N, C) main-head logits of the 2D / 3D network, or null
+  const float* zx[2];        // (N, C) logits of the head the KL term trains (== zm without a dual head), or null: no KL
+  const int64_t* y[2];       // (N,) labels, or null: no CE and no confusion matrix
+  const float* w;            // (C,) class weights or null
+  int64_t ignore;
+  int N, C;
+  int64_t* conf[2];          // (C, C) int64, rows = label, ADDED to; or null
+  const uint8_t* acc_mask;   // (N,) or null
+  int64_t* acc_out;          // [2]: #(mask && argmax(zm[1]) == y[1]), #mask; ADDED to
+  double* partial;           // [PL_NPART][gridDim.x]
+  int* status;
+};
+
+// first maximal index; a NaN wins (torch.argmax, ev_row_stat of evaluate.hip)
+__device__ __forceinline__ int row_argmax(const float* __restrict__ z, int C) {
+  float mx = z[0];
+  int arg = 0;
+  for (int c = 1; c < C; ++c) {
+    const float v = z[c];
+    if (v > mx || (v != v && mx == mx)) { mx = v; arg = c; }
+  }
+  return arg;
+}
+
+// one row's KL term, the loop of k_kl_partial
+__device__ __forceinline__ float kl_row(const float* __restrict__ ar, float la, const float* __restrict__ br, float lb, int C) {
+  float t = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float lq = br[c] - lb, q = expf(lq);
+    t += (q > 0.f) ? q * (lq - (ar[c] - la)) : 0.f;
+  }
+  return t;
+}
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_point_losses(PointLossArgs a) {
+  extern __shared__ int pl_hist[];   // [#matrices][C][C]
+  __shared__ double lds[8];
+  __shared__ int pl_acc[2];
+  const int C = a.C, CC = C * C;
+  int* hist[2] = {a.conf[0] ? pl_hist : nullptr, a.conf[1] ? pl_hist + (a.conf[0] ? CC : 0) : nullptr};
+  const int nh = ((a.conf[0] ? 1 : 0) + (a.conf[1] ? 1 : 0)) * CC;
+  for (int b = threadIdx.x; b < nh; b += blockDim.x) pl_hist[b] = 0;
+  if (threadIdx.x < 2) pl_acc[threadIdx.x] = 0;
+  __syncthreads();
+  const bool ce[2] = {a.zm[0] && a.y[0], a.zm[1] && a.y[1]};
+  const bool kl[2] = {a.zx[0] && a.zm[1], a.zx[1] && a.zm[0]};   // the target of a network's KL is the other's main head
+
+  double num[2] = {0.0, 0.0}, den[2] = {0.0, 0.0}, ksum[2] = {0.0, 0.0};
+  int hit = 0, seen = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.N; i += gridDim.x * blockDim.x) {
+    int64_t yi[2] = {0, 0};
+    bool keep[2] = {false, false};
+    float lm[2] = {0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (ce[k]) {
+        yi[k] = a.y[k][i];
+        if (yi[k] != a.ignore) {
+          if (yi[k] < 0 || yi[k] >= C) atomicOr(a.status, 1);
+          else keep[k] = true;
+        }
+      }
+      if (keep[k] || kl[1 - k] || (kl[k] && a.zx[k] == a.zm[k])) lm[k] = row_lse(a.zm[k] + (int64_t)i * C, C);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const float* zr = a.zm[k] + (int64_t)i * C;
+      if (keep[k]) {
+        const float wi = a.w ? a.w[yi[k]] : 1.f;
+        num[k] += (double)(wi * (lm[k] - zr[yi[k]]));
+        den[k] += (double)wi;
+      }
+      if (kl[k]) {
+        const float* ar = a.zx[k] + (int64_t)i * C;
+        const float la = a.zx[k] == a.zm[k] ? lm[k] : row_lse(ar, C);
+        ksum[k] += (double)kl_row(ar, la, a.zm[1 - k] + (int64_t)i * C, lm[1 - k], C);
+      }
+      const bool masked = k == 1 && a.acc_mask && a.acc_mask[i];
+      if ((hist[k] && keep[k]) || masked) {
+        const int arg = row_argmax(zr, C);
+        if (hist[k] && keep[k]) atomicAdd(&hist[k][(int)yi[k] * C + arg], 1);
+        if (masked) { seen += 1; hit += (int64_t)arg == yi[k] ? 1 : 0; }
+      }
+    }
+  }
+  if (a.acc_mask) {
+    hit = wave_sum_i(hit);
+    seen = wave_sum_i(seen);
+    if ((threadIdx.x & 63) == 0 && seen) { atomicAdd(&pl_acc[0], hit); atomicAdd(&pl_acc[1], seen); }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < nh; b += blockDim.x) {
+    int64_t* dst = b < CC && a.conf[0] ? a.conf[0] + b : a.conf[1] + (b - (a.conf[0] ? CC : 0));
+    if (pl_hist[b]) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)pl_hist[b]);
+  }
+  if (a.acc_mask && threadIdx.x < 2 && pl_acc[threadIdx.x])
+    atomicAdd(reinterpret_cast<unsigned long long*>(a.acc_out + threadIdx.x), (unsigned long long)pl_acc[threadIdx.x]);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (ce[k]) {
+      const double sn = block_sum_d(num[k], lds);
+      const double sd = block_sum_d(den[k], lds);
+      if (threadIdx.x == 0) { a.partial[(3 * k) * gridDim.x + blockIdx.x] = sn; a.partial[(3 * k + 1) * gridDim.x + blockIdx.x] = sd; }
+    }
+    if (kl[k]) {
+      const double s = block_sum_d(ksum[k], lds);
+      if (threadIdx.x == 0) a.partial[(3 * k + 2) * gridDim.x + blockIdx.x] = s;
+    }
+  }
+}
+
+// One block; has: bit 0 / 1 = CE / KL of the 2D network, bit 2 / 3 of the 3D network.  scalars: ce, den, kl per network.
+__global__ void k_point_losses_finalize(const double* __restrict__ partial, int n, int has, double scale, float* __restrict__ scalars) {
+  __shared__ double lds[8];
+  for (int k = 0; k < 2; ++k) {
+    if (has >> (2 * k) & 1) {
+      const double* p = partial + (size_t)(3 * k) * n;
+      double a = 0.0, b = 0.0;
+      for (int i = threadIdx.x; i < n; i += blockDim.x) { a += p[i]; b += p[n + i]; }
+      const double sn = block_sum_d(a, lds);
+      const double sd = block_sum_d(b, lds);
+      if (threadIdx.x == 0) { scalars[3 * k] = (float)(sn / sd); scalars[3 * k + 1] = (float)sd; }
+    }
+    if (has >> (2 * k + 1) & 1) {
+      const double* p = partial + (size_t)(3 * k + 2) * n;
+      double acc = 0.0;
+      for (int i = threadIdx.x; i < n; i += blockDim.x) acc += p[i];
+      const double s = block_sum_d(acc, lds);
+      if (threadIdx.x == 0) scalars[3 * k + 2] = (float)(s * scale);
+    }
+  }
+}
+
+// The sum of a row's CE and KL gradient parts on a shared head: one rounding of the two finished parts, as a tensor add of
+// k_wce_bwd's and k_kl_bwd's results gives -- neither part's multiply may be contracted into this add.  The add is written
+// out under the pragma: __fadd_rn is a plain `x + y` in the HIP headers, compiled with THEIR contraction setting, and was fused
+// with the KL part's multiply into one v_pk_fma_f32.
+__device__ __forceinline__ float add_parts(float ce_part, float kl_part) {
+#pragma clang fp contract(off)
+  return ce_part + kl_part;
+}
+
+// One network's gradients: dz_main = d(g[0] ce)/dz_main (k_wce_bwd's expression), dz_xm = d(g[1] kl)/dz_xm (k_kl_bwd's);
+// on a shared head (z_xm == z_main, dz_xm == dz_main) the sum of the two.
+__global__ __launch_bounds__(LOSS_BLOCK) void k_point_losses_bwd(const float* __restrict__ z_main, const float* __restrict__ z_xm,
+                                                                  const float* __restrict__ z_other, const int64_t* __restrict__ y,
+                                                                  const float* __restrict__ w, int N, int C, int64_t ignore,
+                                                                  const float* __restrict__ den, const float* __restrict__ g,
+                                                                  float* dz_main, float* dz_xm) {
+  const bool ce = y != nullptr, kl = z_other != nullptr, shared = kl && z_xm == z_main;
+  const float gce = ce ? g[0] / *den : 0.f;
+  const float gkl = kl ? g[1] / (float)N : 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
+    int64_t yi = 0;
+    bool keep = false;
+    if (ce) {
+      yi = y[i];
+      keep = !(yi == ignore || yi < 0 || yi >= C);
+    }
+    const float* zr = z_main + (int64_t)i * C;
+    float l = 0.f, s = 0.f;
+    if (keep) {
+      l = row_lse(zr, C);
+      s = gce * (w ? w[yi] : 1.f);
+    }
+    if (shared) {
+      const float* br = z_other + (int64_t)i * C;
+      const float la = keep ? l : row_lse(zr, C), lb = row_lse(br, C);
+      float* d = dz_main + (int64_t)i * C;
+      for (int c = 0; c < C; ++c) {
+        const float pk = gkl * (expf(zr[c] - la) - expf(br[c] - lb));
+        if (ce) d[c] = add_parts(keep ? s * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f)) : 0.f, pk);
+        else d[c] = pk;
+      }
+      continue;
+    }
+    if (ce) {
+      float* d = dz_main + (int64_t)i * C;
+      if (keep) for (int c = 0; c < C; ++c) d[c] = s * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f));
+      else for (int c = 0; c < C; ++c) d[c] = 0.f;
+    }
+    if (kl) {
+      const float* ar = z_xm + (int64_t)i * C;
+      const float* br = z_other + (int64_t)i * C;
+      const float la = row_lse(ar, C), lb = row_lse(br, C);
+      for (int c = 0; c < C; ++c) dz_xm[(int64_t)i * C + c] = gkl * (expf(ar[c] - la) - expf(br[c] - lb));
+    }
+  }
+}
+
+MOPA_API size_t mopa_point_losses_workspace_bytes(int64_t n_rows) { return align_up((size_t)PL_NPART * PL_MAXGRID * sizeof(double), 256); }
+
+// z*_main / z*_xm (N, C) fp32 contiguous; a network's KL term exists when its z*_xm and the OTHER network's z*_main are given
+// (z*_xm may equal z*_main: no dual head), its CE term and confusion matrix when its z*_main and y are.  y2 / y3 (N,) int64,
+// may be the same pointer.  class_weight (C,) or null.  scalars fp32[8]: ce_2d, den_2d, kl_2d, ce_3d, den_3d, kl_3d, two spare;
+// the entries of absent terms are left untouched.  conf_2d / conf_3d (C, C) int64, rows = label, ADDED to, nullable.
+// acc_mask (N,) uint8 nullable with acc_out int64[2], ADDED to: #(mask && argmax(z3_main) == y3), #mask.
+// status: device int, bit0 set when a label is outside [0,C) and != ignore (as mopa_wce_fwd).
+MOPA_API int mopa_point_losses_fwd(const float* z2_main, const float* z2_xm, const float* z3_main, const float* z3_xm,
+                                   const int64_t* y2, const int64_t* y3, const float* class_weight, int32_t N, int32_t C,
+                                   int64_t ignore_index, float* scalars, int64_t* conf_2d, int64_t* conf_3d,
+                                   const uint8_t* acc_mask, int64_t* acc_out, int32_t* status, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  if (N <= 0 || C <= 0 || C > MAXC || !scalars) return MOPA_ERR_ARG;
+  if ((y2 && !z2_main) || (y3 && !z3_main) || ((y2 || y3) && !status)) return MOPA_ERR_ARG;
+  if ((conf_2d && !y2) || (conf_3d && !y3)) return MOPA_ERR_ARG;
+  if (acc_mask && (!y3 || !acc_out)) return MOPA_ERR_ARG;
+  const int has = (y2 ? 1 : 0) | (z2_xm && z3_main ? 2 : 0) | (y3 ? 4 : 0) | (z3_xm && z2_main ? 8 : 0);
+  if (!has) return MOPA_ERR_ARG;
+  if (ws_bytes < mopa_point_losses_workspace_bytes(N)) return MOPA_ERR_WORKSPACE;
+  PointLossArgs a;
+  a.zm[0] = z2_main; a.zm[1] = z3_main; a.zx[0] = z2_xm; a.zx[1] = z3_xm;
+  a.y[0] = y2; a.y[1] = y3; a.w = class_weight; a.ignore = ignore_index;
+  a.N = N; a.C = C;
+  a.conf[0] = conf_2d; a.conf[1] = conf_3d;
+  a.acc_mask = acc_mask; a.acc_out = acc_out;
+  a.partial = (double*)ws; a.status = status;
+  hipStream_t st = (hipStream_t)stream;
+  const int g = stream_grid(N, LOSS_BLOCK);   // <= PL_MAXGRID
+  const size_t lds = (size_t)((conf_2d ? 1 : 0) + (conf_3d ? 1 : 0)) * C * C * sizeof(int);   // <= 32 KB at MAXC
+  k_point_losses<<<g, LOSS_BLOCK, lds, st>>>(a);
+  k_point_losses_finalize<<<1, 256, 0, st>>>((const double*)ws, g, has, 1.0 / N, scalars);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// One network's backward.  y null: no CE part; z_other_main (the detached KL target) null: no KL part.  den: the network's
+// normaliser in `scalars`; g fp32[2]: upstream gradients of (ce, kl).  z_xm == z_main (shared head) needs dz_xm == dz_main,
+// which then receives the sum of the two parts; otherwise dz_main gets the CE part and dz_xm the KL part.
+MOPA_API int mopa_point_losses_bwd(const float* z_main, const float* z_xm, const float* z_other_main, const int64_t* y,
+                                   const float* class_weight, int32_t N, int32_t C, int64_t ignore_index, const float* den,
+                                   const float* g, float* dz_main, float* dz_xm, void* stream) {
+  if (N <= 0 || C <= 0 || C > MAXC || !g) return MOPA_ERR_ARG;
+  if (!y && !z_other_main) return MOPA_ERR_ARG;
+  if (y && (!z_main || !den || !dz_main)) return MOPA_ERR_ARG;
+  if (z_other_main && (!z_xm || !dz_xm)) return MOPA_ERR_ARG;
+  if (z_xm && (z_xm == z_main) != (dz_xm == dz_main)) return MOPA_ERR_ARG;
+  k_point_losses_bwd<<<stream_grid(N, LOSS_BLOCK), LOSS_BLOCK, 0, (hipStream_t)stream>>>(
+      z_main, z_xm, z_other_main, y, class_weight, N, C, ignore_index, den, g, dz_main, dz_xm);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
 // ------------------------------------------------------------------------------------------ softmax over the last dim
 __global__ void k_softmax_fwd(const float* __restrict__ z, int64_t N, int C, float* __restrict__ p) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {

@@ -20,6 +20,15 @@ class SegIoU(object):
             add = torch.bincount(inds, minlength=n * n).reshape(n, n)
             self.mat = add if self.mat is None else self.mat + add
 
+    def add_matrix(self, mat):
+        """Accumulate a confusion matrix computed elsewhere (mopa_amd.trainloss.point_losses): int64 (n, n), rows = label.  Stays on the
+        matrix's device and makes no host sync."""
+        n = self.num_classes
+        if mat.dtype != torch.int64 or tuple(mat.shape) != (n, n):
+            raise ValueError(f"SegIoU.add_matrix: expected an int64 ({n}, {n}) matrix, got {mat.dtype} {tuple(mat.shape)}")
+        with torch.no_grad():
+            self.mat = mat if self.mat is None else self.mat.to(mat.device) + mat
+
     def reset(self):
         self.mat = None
 

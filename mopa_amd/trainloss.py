@@ -1,0 +1,201 @@
+"""The per-point loss-and-metric block of one domain half in one device pass (csrc/losses.hip: mopa_point_losses_fwd / _bwd).
+
+``point_losses`` replaces, between the forward and backward passes of ``mopa/train/train_xmuda_mopa.py:353-418`` (source),
+``:437-469`` (target) and ``:563-576`` (the VGI batch): the two ``F.cross_entropy`` calls, the two cross-modal ``F.kl_div`` calls,
+the two ``SegIoU.update_dict`` calls and ``pc_mm_acc`` -- one forward launch pair for everything, one backward launch per network,
+and no host read (``seg_ce`` x2 + ``xm_kl`` x2 are 8 forward and 4 backward launches, ``update_dict`` syncs the host twice per call).
+Every scalar and every gradient has the bits ``seg_ce`` / ``xm_kl`` give on the same tensors.
+
+The two networks keep separate autograd nodes, as the reference backpropagates ``sum(loss_2d)`` and ``sum(loss_3d)`` separately:
+a node takes its own network's logits only, the other network's enter detached (see ``xm_kl``).
+"""
+from __future__ import annotations
+
+import torch
+
+from ._lib import call, ptr, query, stream, workspace
+from .common.utils import loss as _loss
+
+
+class PointLosses:
+    """ce_2d, kl_2d, ce_3d, kl_3d: 0-d tensors with autograd (None where the term is absent); acc: int64[2] on the device
+    (#masked rows predicted right, #masked rows) or None; status: int32[1], bit 0 = a label outside [0, C) that is not ignore_index."""
+    __slots__ = ("ce_2d", "kl_2d", "ce_3d", "kl_3d", "acc", "status")
+
+    def __init__(self):
+        self.ce_2d = self.kl_2d = self.ce_3d = self.kl_3d = self.acc = self.status = None
+
+
+class _Net:
+    """What one network's node needs: its logits (detached, fp32, contiguous), the detached KL target, labels and the shared result."""
+
+    def __init__(self, k, zm, zx, other, y, w, ignore_index, scalars):
+        self.k, self.zm, self.zx, self.other, self.y, self.w, self.ignore_index, self.scalars = k, zm, zx, other, y, w, ignore_index, scalars
+
+
+class _NetTerms(torch.autograd.Function):
+    """(ce, kl) of one network from the shared forward result; backward = the one mopa_point_losses_bwd call of that network.
+    `z_main` / `z_xm` are the network's own logits where they receive a gradient (None otherwise)."""
+
+    @staticmethod
+    def forward(ctx, net, z_main, z_xm):
+        ctx.net = net
+        ctx.dtypes = (None if z_main is None else z_main.dtype, None if z_xm is None else z_xm.dtype)
+        sc, k = net.scalars, net.k
+        return (sc[3 * k] if net.y is not None else None), (sc[3 * k + 2] if net.other is not None else None)
+
+    @staticmethod
+    def backward(ctx, g_ce, g_kl):
+        net = ctx.net
+        zm, zx = net.zm, net.zx
+        ref = zm if zm is not None else zx
+        N, C = ref.shape
+        zero = None
+        if g_ce is None or g_kl is None:
+            zero = torch.zeros((), dtype=torch.float32, device=ref.device)
+        g = torch.stack([(zero if g_ce is None else g_ce).float(), (zero if g_kl is None else g_kl).float()])
+        has_ce, has_kl = net.y is not None, net.other is not None
+        shared = has_kl and zx is zm
+        dz_main = torch.empty_like(zm) if (has_ce or shared) else None
+        dz_xm = dz_main if shared else (torch.empty_like(zx) if has_kl else None)
+        call("mopa_point_losses_bwd", ptr(zm) if (has_ce or shared) else None, ptr(zx) if has_kl else None, ptr(net.other), ptr(net.y),
+             ptr(net.w), N, C, net.ignore_index, ptr(net.scalars, 3 * net.k + 1), ptr(g), ptr(dz_main), ptr(dz_xm), stream())
+        dm = dz_main if ctx.needs_input_grad[1] else None
+        dx = dz_xm if ctx.needs_input_grad[2] else None
+        if dm is not None and dm.dtype != ctx.dtypes[0]:
+            dm = dm.to(ctx.dtypes[0])
+        if dx is not None and dx.dtype != ctx.dtypes[1]:
+            dx = dx.to(ctx.dtypes[1])
+        return None, dm, dx
+
+
+def _logits(preds, dual_head):
+    """-> (main, xm) graph tensors of one network's output dict; xm is main without a dual head."""
+    if preds is None:
+        return None, None
+    main = preds["seg_logit"]
+    return main, (preds["seg_logit2"] if dual_head else main)
+
+
+def _flat(t):
+    d = t.detach()
+    return d if (d.dtype == torch.float32 and d.is_contiguous()) else d.contiguous().float()
+
+
+def point_losses(preds_2d, preds_3d, *, label=None, label_2d=None, label_3d=None, weight=None, kl=True, dual_head_2d=None,
+                 ignore_index=-100, metric_2d=None, metric_3d=None, acc_mask=None, dual=None) -> PointLosses:
+    """CE, cross-modal KL, SegIoU update and masked accuracy of one batch of points for both networks.
+
+    preds_2d / preds_3d: the models' output dicts (``seg_logit`` (N, C), and ``seg_logit2`` when the head is dual), either may be None
+    (the VGI batch has 3D only).  The 2D KL term trains ``seg_logit2`` when ``dual_head_2d`` (default: ``seg_logit2`` is in the dict), the
+    3D one ``preds_3d['seg_logit2']`` when present; both compare with the other network's detached ``seg_logit``.
+    label: (N,) labels of both networks (source half: ``seg_label``); label_2d / label_3d: one network's (target half: the pseudo
+    labels; VGI batch: ``label_3d=cat_ps_label``).  A network without labels has no CE term and no metric update.
+    weight: (C,) class weights of ``F.cross_entropy`` or None.  kl=False: no KL terms.
+    metric_2d / metric_3d: ``SegIoU``; receive this batch's confusion matrix through ``add_matrix`` (no host sync).
+    acc_mask: (N,) bool / uint8; ``.acc`` is then (#rows with the mask set whose 3D prediction equals label_3d, #rows with the mask set).
+    dual: a ``mopa_amd.step.DualStream``; the 3D node is created on its side stream, so its backward -- and with it the whole 3D
+    backward -- is queued there (``DualStream.on_side`` / ``backward_on_side``).
+
+    The caller applies the lambdas to the returned scalars.  Labels outside [0, C) that are not ``ignore_index`` are dropped and
+    flagged in ``.status``; ``MOPA_VALIDATE_LABELS=1`` reads it back and raises, as ``seg_ce`` does.  N == 0: nothing is launched,
+    the terms are NaN (``F.cross_entropy`` / ``.mean()`` of nothing) and the metrics untouched.  CUDA tensors only."""
+    if preds_2d is None and preds_3d is None:
+        raise ValueError("point_losses: both preds_2d and preds_3d are None")
+    if dual_head_2d is None or dual_head_2d is ...:
+        dual_head_2d = preds_2d is not None and "seg_logit2" in preds_2d
+    g2m, g2x = _logits(preds_2d, bool(dual_head_2d))
+    g3m, g3x = _logits(preds_3d, preds_3d is not None and "seg_logit2" in preds_3d)
+    ref = g2m if g2m is not None else g3m
+    if not ref.is_cuda:
+        raise RuntimeError("point_losses: the logits are CPU tensors; the hot path has no CPU fallback")
+    dev = ref.device
+    N, C = ref.shape
+    for t in (g2m, g2x, g3m, g3x):
+        if t is not None and (tuple(t.shape) != (N, C) or t.device != dev):
+            raise RuntimeError(f"point_losses: logits of shape {tuple(t.shape)} on {t.device}, expected {(N, C)} on {dev}")
+    y2 = label_2d if label_2d is not None else label
+    y3 = label_3d if label_3d is not None else label
+    y2 = None if (y2 is None or g2m is None) else y2
+    y3 = None if (y3 is None or g3m is None) else y3
+    has_kl = bool(kl) and g2m is not None and g3m is not None
+    out = PointLosses()
+
+    if N == 0:
+        nan = float("nan")
+        if y2 is not None:
+            out.ce_2d = g2m.sum() * nan
+        if y3 is not None:
+            out.ce_3d = g3m.sum() * nan
+        if has_kl:
+            out.kl_2d, out.kl_3d = g2x.sum() * nan, g3x.sum() * nan
+        if acc_mask is not None and y3 is not None:
+            out.acc = torch.zeros(2, dtype=torch.int64, device=dev)
+        out.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        return out
+
+    def lab(y):
+        if y is None:
+            return None
+        if y.numel() != N:
+            raise RuntimeError(f"point_losses: {y.numel()} labels for {N} rows")
+        return y.to(device=dev, dtype=torch.int64).contiguous()
+
+    same = y2 is y3
+    y2 = lab(y2)
+    y3 = y2 if (same and y2 is not None) else lab(y3)
+    w = None if weight is None else weight.to(dev).contiguous().float()
+    if w is not None and w.numel() != C:
+        raise RuntimeError(f"point_losses: {w.numel()} class weights for {C} classes")
+    for m, y in ((metric_2d, y2), (metric_3d, y3)):
+        if m is not None and y is not None and m.num_classes != C:
+            raise ValueError(f"point_losses: a metric of {m.num_classes} classes for logits of {C}")
+    want2, want3 = metric_2d is not None and y2 is not None, metric_3d is not None and y3 is not None
+    mask = None
+    if acc_mask is not None and y3 is not None:
+        if acc_mask.numel() != N:
+            raise RuntimeError(f"point_losses: acc_mask of {acc_mask.numel()} entries for {N} rows")
+        mask = acc_mask.to(dev).contiguous()
+        if mask.dtype != torch.uint8:
+            mask = (mask if mask.dtype == torch.bool else mask.ne(0)).view(torch.uint8)
+
+    z2m, z3m = (None if g2m is None else _flat(g2m)), (None if g3m is None else _flat(g3m))
+    z2x = None if not has_kl else (z2m if g2x is g2m else _flat(g2x))
+    z3x = None if not has_kl else (z3m if g3x is g3m else _flat(g3x))
+
+    # one zero-filled int64 block: conf_2d | conf_3d | acc | status (the kernel adds to the first three and ORs into the last)
+    ints = torch.zeros(2 * C * C + 3, dtype=torch.int64, device=dev)
+    conf2, conf3 = ints[:C * C].view(C, C), ints[C * C:2 * C * C].view(C, C)
+    acc = ints[2 * C * C:2 * C * C + 2]
+    status = ints[2 * C * C + 2:].view(torch.int32)[:1]
+    scalars = torch.empty(8, dtype=torch.float32, device=dev)
+    ws = workspace.get(query("mopa_point_losses_workspace_bytes", N), dev)
+    call("mopa_point_losses_fwd", ptr(z2m), ptr(z2x), ptr(z3m), ptr(z3x), ptr(y2), ptr(y3), ptr(w), N, C, ignore_index, ptr(scalars),
+         ptr(conf2) if want2 else None, ptr(conf3) if want3 else None, ptr(mask), ptr(acc) if mask is not None else None, ptr(status),
+         ptr(ws), ws.numel(), stream())
+    out.status = status
+    if mask is not None:
+        out.acc = acc
+    if want2:
+        metric_2d.add_matrix(conf2)
+    if want3:
+        metric_3d.add_matrix(conf3)
+    if _loss.VALIDATE_LABELS and int(status.item()) != 0:   # a host sync: debugging / validation runs only
+        raise IndexError(f"point_losses: a label is outside [0, {C}) and is not ignore_index {ignore_index} "
+                         "(F.cross_entropy raises 'Target out of bounds' here)")
+
+    if y2 is not None or has_kl:
+        net = _Net(0, z2m, z2x, z3m if has_kl else None, y2, w, ignore_index, scalars)
+        shared = has_kl and z2x is z2m
+        out.ce_2d, out.kl_2d = _NetTerms.apply(net, g2m if (y2 is not None or shared) else None, g2x if (has_kl and not shared) else None)
+    if y3 is not None or has_kl:
+        net = _Net(1, z3m, z3x, z2m if has_kl else None, y3, w, ignore_index, scalars)
+        shared = has_kl and z3x is z3m
+        args = (net, g3m if (y3 is not None or shared) else None, g3x if (has_kl and not shared) else None)
+        if dual is not None:
+            # the side stream waits for the fused forward; the node's backward reads these there
+            with dual.on_side(z3m, z3x, z2m if has_kl else None, y3, w, scalars):
+                out.ce_3d, out.kl_3d = _NetTerms.apply(*args)
+        else:
+            out.ce_3d, out.kl_3d = _NetTerms.apply(*args)
+    return out

@@ -1,0 +1,587 @@
+"""The fused per-point training losses (csrc/losses.hip: mopa_point_losses_fwd / _bwd, mopa_amd/trainloss.py::point_losses).
+
+Every scalar and every gradient is compared BIT FOR BIT with the single entry points on the same tensors (mopa_wce_fwd / _bwd,
+mopa_softmax_kl_fwd / _bwd; a shared head's gradient with the torch.add of the two), the integers with numpy restatements and with
+SegIoU.update_dict, and the arithmetic once more with float64 on the CPU.  Shapes: one row, below / above one block of 256 rows,
+several blocks with a ragged tail, and 524,588 rows -- every thread of the 2048 x 256 grid takes a second row, the last 300 a third."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = ((1, 2), (63, 5), (257, 5), (1000, 11), (4099, 10), (524588, 5))
+MAXC = 64
+SENTINEL = -7.25
+
+
+def _lib():
+    from mopa_amd import _lib
+    return _lib
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
+
+
+@functools.lru_cache(maxsize=None)
+def _case(N, C):
+    """Seeded CPU inputs: four logit matrices ~ N(0, 2), two label vectors with ~30 % of -100, class weights.  Never written."""
+    rng = np.random.Generator(np.random.PCG64(1000 * C + N % 9973))
+    z = [torch.from_numpy(rng.standard_normal((N, C), dtype=np.float32) * 2) for _ in range(4)]
+    ys = []
+    for _ in range(2):
+        y = rng.integers(0, C, N)
+        y[rng.random(N) < 0.3] = -100
+        if N == 1:
+            y[:] = C - 1
+        ys.append(torch.from_numpy(y))
+    w = torch.from_numpy(rng.uniform(1, 3, C).astype(np.float32))
+    return {"z2m": z[0], "z2x": z[1], "z3m": z[2], "z3x": z[3], "y": ys[0], "y_alt": ys[1], "w": w}
+
+
+@functools.lru_cache(maxsize=2)
+def _dev(N, C):
+    return {k: v.cuda() for k, v in _case(N, C).items()}
+
+
+def _ws(name, N):
+    lib = _lib()
+    return torch.empty(max(lib.query(name, N), 256), dtype=torch.uint8, device="cuda")
+
+
+# ------------------------------------------------------------------------------------------------ the single entry points
+def _ce(z, y, w, ignore=-100):
+    lib = _lib()
+    N, C = z.shape
+    out, status = torch.full((2,), SENTINEL, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+    ws = _ws("mopa_loss_workspace_bytes", N)
+    lib.call("mopa_wce_fwd", lib.ptr(z), lib.ptr(y), lib.ptr(w), N, C, ignore, lib.ptr(out), lib.ptr(out, 1), lib.ptr(status), lib.ptr(ws),
+             ws.numel(), lib.stream())
+    return out, status
+
+
+def _kl(p, q):
+    lib = _lib()
+    N, C = p.shape
+    out = torch.full((1,), SENTINEL, device="cuda")
+    ws = _ws("mopa_loss_workspace_bytes", N)
+    lib.call("mopa_softmax_kl_fwd", lib.ptr(p), lib.ptr(q), N, C, lib.ptr(out), lib.ptr(ws), ws.numel(), lib.stream())
+    return out
+
+
+def _ce_bwd(z, y, w, den, g, ignore=-100):
+    lib = _lib()
+    dz = torch.full_like(z, SENTINEL)
+    lib.call("mopa_wce_bwd", lib.ptr(z), lib.ptr(y), lib.ptr(w), z.shape[0], z.shape[1], ignore, lib.ptr(den), lib.ptr(g), lib.ptr(dz),
+             lib.stream())
+    return dz
+
+
+def _kl_bwd(p, q, g):
+    lib = _lib()
+    dp = torch.full_like(p, SENTINEL)
+    lib.call("mopa_softmax_kl_bwd", lib.ptr(p), lib.ptr(q), p.shape[0], p.shape[1], lib.ptr(g), lib.ptr(dp), lib.stream())
+    return dp
+
+
+# ------------------------------------------------------------------------------------------------ the fused entry points
+def _fwd(z2m, z2x, z3m, z3x, y2, y3, w, N, C, ignore=-100, conf2=None, conf3=None, mask=None, acc=None, scalars=None, ws=None):
+    lib = _lib()
+    if scalars is None:
+        scalars = torch.full((8,), SENTINEL, device="cuda")
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if ws is None:
+        ws = _ws("mopa_point_losses_workspace_bytes", N)
+    lib.call("mopa_point_losses_fwd", lib.ptr(z2m), lib.ptr(z2x), lib.ptr(z3m), lib.ptr(z3x), lib.ptr(y2), lib.ptr(y3), lib.ptr(w), N, C,
+             ignore, lib.ptr(scalars), lib.ptr(conf2), lib.ptr(conf3), lib.ptr(mask), lib.ptr(acc), lib.ptr(status), lib.ptr(ws),
+             ws.numel(), lib.stream())
+    return scalars, status
+
+
+def _bwd(zm, zx, other, y, w, N, C, den, g, shared, ignore=-100):
+    """-> (dz_main, dz_xm); outputs the call does not write stay None."""
+    lib = _lib()
+    like = zm if zm is not None else zx
+    dz_main = torch.full_like(like, SENTINEL) if (y is not None or shared) else None
+    dz_xm = dz_main if shared else (torch.full_like(like, SENTINEL) if other is not None else None)
+    lib.call("mopa_point_losses_bwd", lib.ptr(zm), lib.ptr(zx), lib.ptr(other), lib.ptr(y), lib.ptr(w), N, C, ignore, lib.ptr(den),
+             lib.ptr(g), lib.ptr(dz_main), lib.ptr(dz_xm), lib.stream())
+    return dz_main, dz_xm
+
+
+def _heads(d, dual):
+    return (d["z2m"], d["z2x"] if dual else d["z2m"], d["z3m"], d["z3x"] if dual else d["z3m"])
+
+
+# ------------------------------------------------------------------------------------------------ bits
+@pytest.mark.parametrize("N,C", SHAPES)
+def test_forward_has_the_bits_of_the_single_calls(N, C):
+    d = _dev(N, C)
+    for dual in (True, False):
+        z2m, z2x, z3m, z3x = _heads(d, dual)
+        for w in (None, d["w"]):
+            sc, status = _fwd(z2m, z2x, z3m, z3x, d["y"], d["y"], w, N, C)
+            ce2, ce3 = _ce(z2m, d["y"], w)[0], _ce(z3m, d["y"], w)[0]
+            want = torch.cat([ce2, _kl(z2x, z3m), ce3, _kl(z3x, z2m), torch.full((2,), SENTINEL, device="cuda")])
+            print(N, C, dual, w is not None, sc.tolist(), want.tolist())
+            assert torch.isfinite(sc[:6]).all()
+            assert _same_bits(sc, want), (dual, w is not None)
+            assert torch.equal(sc[:6], want[:6])
+            assert status.item() == 0
+
+
+@pytest.mark.parametrize("N,C", SHAPES)
+def test_backward_has_the_bits_of_the_single_calls(N, C):
+    d = _dev(N, C)
+    y, w = d["y"], d["w"]
+    for dual in (True, False):
+        z2m, z2x, z3m, z3x = _heads(d, dual)
+        sc, _ = _fwd(z2m, z2x, z3m, z3x, y, y, w, N, C)
+        for gs in ((1.0, 1.0), (0.7, 0.1)):
+            g = torch.tensor(gs, device="cuda")
+            for zm, zx, other, den in ((z2m, z2x, z3m, sc[1:2]), (z3m, z3x, z2m, sc[4:5])):
+                dz_main, dz_xm = _bwd(zm, zx, other, y, w, N, C, den, g, shared=not dual)
+                ce_part, kl_part = _ce_bwd(zm, y, w, den, g[0:1]), _kl_bwd(zx, other, g[1:2])
+                if dual:
+                    assert _same_bits(dz_main, ce_part) and _same_bits(dz_xm, kl_part), gs
+                    assert torch.equal(dz_main, ce_part) and torch.equal(dz_xm, kl_part)
+                else:
+                    assert dz_xm is dz_main
+                    want = torch.add(ce_part, kl_part)
+                    assert torch.equal(dz_main, want) and _same_bits(dz_main, want), gs
+
+
+def test_degenerate_forms():
+    N, C = 4099, 10
+    d = _dev(N, C)
+    y, y_alt, w = d["y"], d["y_alt"], d["w"]
+    g = torch.tensor((0.7, 0.1), device="cuda")
+    # 3D only, CE only (the VGI batch): no 2D pointer at all
+    sc, _ = _fwd(None, None, d["z3m"], None, None, y, w, N, C)
+    ce3 = _ce(d["z3m"], y, w)[0]
+    assert _same_bits(sc[3:5], ce3) and (sc[:3] == SENTINEL).all() and (sc[5:] == SENTINEL).all()
+    dz_main, dz_xm = _bwd(d["z3m"], None, None, y, w, N, C, sc[4:5], g, shared=False)
+    assert dz_xm is None and _same_bits(dz_main, _ce_bwd(d["z3m"], y, w, sc[4:5], g[0:1]))
+    # a 3D-only call whose xm head is given has no KL term either: its target does not exist
+    sc2, _ = _fwd(None, None, d["z3m"], d["z3x"], None, y, w, N, C)
+    assert _same_bits(sc2, sc)
+    # KL only: dual heads, then shared heads
+    for dual in (True, False):
+        z2m, z2x, z3m, z3x = _heads(d, dual)
+        sc, status = _fwd(z2m, z2x, z3m, z3x, None, None, None, N, C)
+        assert _same_bits(sc[2:3], _kl(z2x, z3m)) and _same_bits(sc[5:6], _kl(z3x, z2m))
+        assert (sc[[0, 1, 3, 4, 6, 7]] == SENTINEL).all() and status.item() == 0
+        dz_main, dz_xm = _bwd(z2m, z2x, z3m, None, None, N, C, None, g, shared=not dual)
+        assert (dz_main is None) == dual and _same_bits(dz_xm, _kl_bwd(z2x, z3m, g[1:2]))
+    dz_main, dz_xm = _bwd(None, d["z2x"], d["z3m"], None, None, N, C, None, g, shared=False)   # the main head is not needed then
+    assert _same_bits(dz_xm, _kl_bwd(d["z2x"], d["z3m"], g[1:2]))
+    # different labels for the two networks, one network without weights' effect on the other
+    z2m, z2x, z3m, z3x = _heads(d, True)
+    sc, _ = _fwd(z2m, z2x, z3m, z3x, y, y_alt, w, N, C)
+    assert _same_bits(sc[0:2], _ce(z2m, y, w)[0]) and _same_bits(sc[3:5], _ce(z3m, y_alt, w)[0])
+    assert not _same_bits(sc[3:5], _ce(z3m, y, w)[0])
+    # CE of one network only, KL of both
+    sc, _ = _fwd(z2m, z2x, z3m, z3x, y, None, w, N, C)
+    assert _same_bits(sc[0:2], _ce(z2m, y, w)[0]) and (sc[3:5] == SENTINEL).all()
+    assert _same_bits(sc[2:3], _kl(z2x, z3m)) and _same_bits(sc[5:6], _kl(z3x, z2m))
+
+
+def test_all_labels_of_one_network_ignored():
+    N, C = 1000, 11
+    d = _dev(N, C)
+    y, w = d["y"], d["w"]
+    none = torch.full_like(y, -100)
+    g = torch.tensor((0.7, 0.1), device="cuda")
+    for dual in (True, False):
+        z2m, z2x, z3m, z3x = _heads(d, dual)
+        base, _ = _fwd(z2m, z2x, z3m, z3x, y, y, w, N, C)
+        sc, status = _fwd(z2m, z2x, z3m, z3x, none, y, w, N, C)
+        assert torch.isnan(sc[0]) and sc[1].item() == 0 and status.item() == 0
+        assert torch.isnan(_ce(z2m, none, w)[0][0])                     # as the single call (seg_ce) today
+        assert _same_bits(sc[2:6], base[2:6])                           # kl_2d and the whole 3D network: unchanged
+        dz_main, dz_xm = _bwd(z2m, z2x, z3m, none, w, N, C, sc[1:2], g, shared=not dual)
+        kl_part = _kl_bwd(z2x, z3m, g[1:2])
+        if dual:
+            assert (dz_main == 0).all() and _same_bits(dz_xm, kl_part)
+        else:
+            assert torch.equal(dz_main, torch.add(torch.zeros_like(kl_part), kl_part)) and torch.isfinite(dz_main).all()
+        for den in (base, sc):
+            got = _bwd(z3m, z3x, z2m, y, w, N, C, den[4:5], g, shared=not dual)
+            want = (_ce_bwd(z3m, y, w, base[4:5], g[0:1]), _kl_bwd(z3x, z2m, g[1:2]))
+            if dual:
+                assert _same_bits(got[0], want[0]) and _same_bits(got[1], want[1])
+            else:
+                assert _same_bits(got[0], torch.add(*want))
+
+
+def test_out_of_range_labels_are_dropped_and_flagged():
+    N, C = 1000, 11
+    d = _dev(N, C)
+    w = d["w"]
+    bad = d["y"].clone()
+    rows = torch.tensor([3, 700], device="cuda")
+    bad[rows] = torch.tensor([C, -5], device="cuda")
+    clean = bad.clone()
+    clean[rows] = -100
+    g = torch.tensor((0.7, 0.1), device="cuda")
+    z2m, z2x, z3m, z3x = _heads(d, False)
+    res = {}
+    for name, y in (("bad", bad), ("clean", clean)):
+        conf = torch.zeros(2, C, C, dtype=torch.int64, device="cuda")
+        sc, status = _fwd(z2m, z2x, z3m, z3x, y, y, w, N, C, conf2=conf[0], conf3=conf[1])
+        dz = _bwd(z2m, z2x, z3m, y, w, N, C, sc[1:2], g, shared=True)[0]
+        res[name] = (sc, status.item(), conf, dz)
+    assert res["bad"][1] == 1 and res["clean"][1] == 0
+    assert _same_bits(res["bad"][0], res["clean"][0])                  # numerator and normaliser
+    assert torch.equal(res["bad"][2], res["clean"][2]) and int(res["bad"][2][0].sum()) == int((clean != -100).sum())
+    assert _same_bits(res["bad"][3], res["clean"][3])
+    assert _same_bits(res["bad"][3][rows], _kl_bwd(z2x, z3m, g[1:2])[rows] + 0.0)   # no CE part on the dropped rows
+
+
+# ------------------------------------------------------------------------------------------------ float64
+U = 2.0 ** -24
+
+
+def softmax_grad_bound(Z, s):
+    """tests/test_gpu_loss_edges.py: |error| of s * (p_c - t_c), p = exp(z - lse) in fp32, Z = the row's largest |logit|."""
+    return (4.0 + 2.0 * Z) * 2.0 ** -23 * s
+
+
+def _within(got, ref, bound, what, rtol=0.0):
+    got, ref = got.detach().cpu().double(), ref.detach().cpu().double()
+    bound = torch.as_tensor(bound, dtype=torch.float64).expand_as(ref)
+    if rtol:
+        bound = ref.abs() * rtol + bound
+    err = (got - ref).abs()
+    bad = ~(err <= bound)
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {err.numel()} outside the bound, worst |err| {err[bad].max().item():.3e}"
+
+
+@pytest.mark.parametrize("N,C", ((257, 5), (1000, 11)))
+def test_single_head_against_float64(N, C):
+    """Values at rtol 1e-5; a gradient part within softmax_grad_bound of its scale + rtol 1e-4, the shared head's sum within the sum
+    of its two parts' bounds + rtol 1e-4 (the add itself rounds once, 2^-24 of the sum)."""
+    from mopa_amd.trainloss import point_losses
+    c = _case(N, C)
+    y, w = c["y"], c["w"]
+    gc, gk = 0.625, 1.75
+    r2, r3 = c["z2m"].double().requires_grad_(True), c["z3m"].double().requires_grad_(True)
+    keep = y != -100
+    den = w.double()[y[keep]].sum().item()
+    s_ce = torch.where(keep, w.double()[y.clamp(min=0)], torch.zeros((), dtype=torch.float64)) * gc / den
+    Z2, Z3 = c["z2m"].abs().amax(1).double(), c["z3m"].abs().amax(1).double()
+    Z23 = torch.maximum(Z2, Z3)
+    for mine, other, Zm, which in ((r2, r3, Z2, "2d"), (r3, r2, Z3, "3d")):
+        ce_ref = F.cross_entropy(mine, y, weight=w.double())
+        kl_ref = F.kl_div(F.log_softmax(mine, 1), F.softmax(other.detach(), 1), reduction="none").sum(1).mean()
+        bounds = {"ce": softmax_grad_bound(Zm, s_ce)[:, None], "kl": softmax_grad_bound(Z23, gk / N)[:, None]}
+        bounds["sum"] = bounds["ce"] + bounds["kl"]
+        for part in ("ce", "kl", "sum"):
+            z2, z3 = c["z2m"].cuda().requires_grad_(True), c["z3m"].cuda().requires_grad_(True)
+            res = point_losses({"seg_logit": z2}, {"seg_logit": z3}, label=y.cuda(), weight=w.cuda())
+            ce, kl = (res.ce_2d, res.kl_2d) if which == "2d" else (res.ce_3d, res.kl_3d)
+            np.testing.assert_allclose(ce.item(), ce_ref.item(), rtol=1e-5)
+            np.testing.assert_allclose(kl.item(), kl_ref.item(), rtol=1e-5)
+            loss, ref = {"ce": (gc * ce, gc * ce_ref), "kl": (gk * kl, gk * kl_ref), "sum": (gc * ce + gk * kl, gc * ce_ref + gk * kl_ref)}[part]
+            loss.backward()
+            (gref,) = torch.autograd.grad(ref, mine, retain_graph=True)
+            got = z2.grad if which == "2d" else z3.grad
+            assert (z3.grad if which == "2d" else z2.grad) is None
+            _within(got, gref, bounds[part], f"d {part} {which} {N, C}", rtol=1e-4)
+            if part == "kl":
+                assert not (got[~keep.cuda()] == 0).all()
+            if part == "ce":
+                assert (got[~keep.cuda()] == 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ confusion, accuracy
+def _tie_case(N, C):
+    """The case's inputs with the maximum copied into another column on ~8 % of the rows of each main head (two equal maxima), and a
+    20 % mask."""
+    c = _case(N, C)
+    rng = np.random.Generator(np.random.PCG64(N + C))
+    out = {}
+    for k in ("z2m", "z3m"):
+        z = c[k].clone().numpy()
+        rows = np.sort(rng.choice(N, int(np.ceil(0.08 * N)), replace=False))   # an exact count: a draw per row gave 2 of 63
+        assert len(rows) >= 0.05 * N
+        arg = z[rows].argmax(1)
+        col = (arg + rng.integers(1, C, len(rows))) % C
+        z[rows, col] = z[rows, arg]
+        assert ((z == z.max(1, keepdims=True)).sum(1) >= 2).sum() >= 0.05 * N
+        out[k] = torch.from_numpy(z)
+    out["mask"] = torch.from_numpy(rng.random(N) < 0.2)
+    return c, out
+
+
+def _np_conf(z, y, C):
+    mat = np.zeros((C, C), np.int64)
+    y = y.numpy()
+    keep = y != -100
+    np.add.at(mat, (y[keep], np.argmax(z.numpy(), 1)[keep]), 1)
+    return torch.from_numpy(mat)
+
+
+@pytest.mark.parametrize("N,C", ((4099, 10), (63, 5)))
+def test_confusion_and_accuracy(N, C):
+    from mopa_amd.models.metric import SegIoU
+    from mopa_amd.trainloss import point_losses
+    c, t = _tie_case(N, C)
+    y2, y3, mask = c["y"], c["y_alt"], t["mask"]
+    z2, z3 = t["z2m"].cuda(), t["z3m"].cuda()
+    want2, want3 = _np_conf(t["z2m"], y2, C), _np_conf(t["z3m"], y3, C)
+    pred3 = np.argmax(t["z3m"].numpy(), 1)
+    hit, seen = int(((pred3 == y3.numpy()) & mask.numpy()).sum()), int(mask.sum())
+    assert 0 < hit < seen
+    # through the C ABI: two calls ADD into the same matrices and counts
+    conf = torch.zeros(2, C, C, dtype=torch.int64, device="cuda")
+    conf[0, 0, 0], conf[1, C - 1, 0] = 5, 9
+    acc = torch.tensor([100, 1000], device="cuda")
+    m8 = mask.cuda().view(torch.uint8)
+    for _ in range(2):
+        _fwd(z2, z2, z3, z3, y2.cuda(), y3.cuda(), None, N, C, conf2=conf[0], conf3=conf[1], mask=m8, acc=acc)
+    conf[0, 0, 0] -= 5
+    conf[1, C - 1, 0] -= 9
+    assert torch.equal(conf[0].cpu(), 2 * want2) and torch.equal(conf[1].cpu(), 2 * want3)
+    assert acc.tolist() == [100 + 2 * hit, 1000 + 2 * seen]
+    # one matrix only, no accuracy
+    only3 = torch.zeros(C, C, dtype=torch.int64, device="cuda")
+    _fwd(z2, z2, z3, z3, y2.cuda(), y3.cuda(), None, N, C, conf3=only3)
+    assert torch.equal(only3.cpu(), want3)
+    # through point_losses into SegIoU, beside update_dict on the same inputs
+    m2, m3, u2, u3 = SegIoU(C), SegIoU(C), SegIoU(C), SegIoU(C)
+    for _ in range(2):
+        res = point_losses({"seg_logit": z2}, {"seg_logit": z3}, label_2d=y2.cuda(), label_3d=y3.cuda(), metric_2d=m2, metric_3d=m3,
+                           acc_mask=mask.cuda())
+        u2.update_dict({"seg_logit": z2}, {"seg_label": y2.cuda()})
+        u3.update_dict({"seg_logit": z3}, {"seg_label": y3.cuda()})
+        assert res.acc.dtype == torch.int64 and res.acc.tolist() == [hit, seen]
+    assert m2.mat.is_cuda and torch.equal(m2.mat, u2.mat) and torch.equal(m3.mat, u3.mat)
+    assert torch.equal(m2.mat.cpu(), 2 * want2) and torch.equal(m3.mat.cpu(), 2 * want3)
+    assert torch.equal(m3.iou.nan_to_num(-1.0), u3.iou.nan_to_num(-1.0))
+
+
+# ------------------------------------------------------------------------------------------------ point_losses
+def _leaves(N, C, dual):
+    c = _case(N, C)
+    names = ("z2m", "z2x", "z3m", "z3x") if dual else ("z2m", "z3m")
+    L = {k: c[k].cuda().requires_grad_(True) for k in names}
+    p2 = {"seg_logit": L["z2m"]}
+    p3 = {"seg_logit": L["z3m"]}
+    if dual:
+        p2["seg_logit2"], p3["seg_logit2"] = L["z2x"], L["z3x"]
+    return L, p2, p3
+
+
+@pytest.mark.parametrize("dual", (True, False))
+def test_point_losses_equals_seg_ce_and_xm_kl(dual):
+    from mopa_amd.common.utils.loss import seg_ce, xm_kl
+    from mopa_amd.trainloss import point_losses
+    N, C = 4099, 10
+    c = _case(N, C)
+    y, w = c["y"].cuda(), c["w"].cuda()
+    L, p2, p3 = _leaves(N, C, dual)
+    res = point_losses(p2, p3, label=y, weight=w)
+    (res.ce_2d + 0.1 * res.kl_2d).backward()
+    (res.ce_3d + 0.1 * res.kl_3d).backward()
+    R, q2, q3 = _leaves(N, C, dual)
+    x2, x3 = q2.get("seg_logit2", q2["seg_logit"]), q3.get("seg_logit2", q3["seg_logit"])
+    ce2, kl2 = seg_ce(q2["seg_logit"], y, w), xm_kl(x2, q3["seg_logit"])
+    ce3, kl3 = seg_ce(q3["seg_logit"], y, w), xm_kl(x3, q2["seg_logit"])
+    (ce2 + 0.1 * kl2).backward()
+    (ce3 + 0.1 * kl3).backward()
+    for got, want in ((res.ce_2d, ce2), (res.kl_2d, kl2), (res.ce_3d, ce3), (res.kl_3d, kl3)):
+        assert got.dim() == 0 and _same_bits(got, want)
+    for k in L:
+        assert _same_bits(L[k].grad, R[k].grad), k
+    assert res.status.item() == 0 and res.acc is None
+
+
+@pytest.mark.parametrize("dual", (True, False))
+def test_autograd_structure(dual):
+    from mopa_amd.trainloss import point_losses
+    N, C = 257, 5
+    y = _case(N, C)["y"].cuda()
+    L, p2, p3 = _leaves(N, C, dual)
+    res = point_losses(p2, p3, label=y)
+    (res.ce_2d + 0.1 * res.kl_2d).backward()                           # no retain_graph: the two networks share no node
+    assert all((L[k].grad is None) == k.startswith("z3") for k in L)
+    (res.ce_3d + 0.1 * res.kl_3d).backward()
+    assert all(L[k].grad is not None and torch.isfinite(L[k].grad).all() for k in L)
+    L, p2, p3 = _leaves(N, C, dual)
+    res = point_losses(p2, p3, label=y)
+    (res.ce_3d + 0.1 * res.kl_3d).backward()
+    assert all((L[k].grad is None) == k.startswith("z2") for k in L)
+    # the VGI batch: 3D only, no KL
+    L, _, p3 = _leaves(N, C, dual)
+    res = point_losses(None, p3, label_3d=y, acc_mask=y != -100)
+    assert res.ce_2d is None and res.kl_2d is None and res.kl_3d is None and res.acc is not None
+    res.ce_3d.backward()
+    assert L["z3m"].grad is not None and (not dual or L["z3x"].grad is None)
+    # no labels: KL only; kl=False: CE only
+    L, p2, p3 = _leaves(N, C, dual)
+    res = point_losses(p2, p3)
+    assert res.ce_2d is None and res.ce_3d is None
+    (res.kl_2d * 2).backward()
+    assert L["z2x" if dual else "z2m"].grad is not None and L["z3m"].grad is None and (not dual or L["z2m"].grad is None)
+    res = point_losses(p2, p3, label=y, kl=False)
+    assert res.kl_2d is None and res.kl_3d is None and res.ce_2d is not None and res.ce_3d is not None
+
+
+class _Recorder:
+    """trainloss.call with the entry-point names (and the stream argument) written down."""
+
+    def __init__(self, monkeypatch, trainloss):
+        self.names, self.streams, inner = [], [], trainloss.call
+
+        def call(name, *args):
+            self.names.append(name)
+            self.streams.append(args[-1])
+            return inner(name, *args)
+        monkeypatch.setattr(trainloss, "call", call)
+
+
+@pytest.mark.parametrize("dual", (True, False))
+def test_launch_count(dual, monkeypatch):
+    from mopa_amd import trainloss
+    from mopa_amd.common.utils import loss as single
+    from mopa_amd.models.metric import SegIoU
+    N, C = 1000, 11
+    c = _case(N, C)
+    rec = _Recorder(monkeypatch, trainloss)
+    other = _Recorder(monkeypatch, single)
+    L, p2, p3 = _leaves(N, C, dual)
+    res = trainloss.point_losses(p2, p3, label=c["y"].cuda(), weight=c["w"].cuda(), metric_2d=SegIoU(C), metric_3d=SegIoU(C))
+    assert rec.names == ["mopa_point_losses_fwd"]
+    (res.ce_2d + 0.1 * res.kl_2d).backward()
+    (res.ce_3d + 0.1 * res.kl_3d).backward()
+    assert rec.names == ["mopa_point_losses_fwd", "mopa_point_losses_bwd", "mopa_point_losses_bwd"]
+    assert other.names == []                                           # no mopa_wce_* / mopa_softmax_kl_*
+
+
+@pytest.mark.parametrize("dual_head", (True, False))
+def test_dual_stream_runs_the_3d_backward_on_the_side_stream(dual_head, monkeypatch):
+    from mopa_amd import trainloss
+    from mopa_amd.step import DualStream
+    N, C = 4099, 10
+    c = _case(N, C)
+    y, w = c["y"].cuda(), c["w"].cuda()
+    runs = {}
+    for use_dual in (False, True):
+        dual = DualStream("cuda") if use_dual else None
+        rec = _Recorder(monkeypatch, trainloss)
+        L, p2, p3 = _leaves(N, C, dual_head)
+        main = torch.cuda.current_stream().cuda_stream
+        res = trainloss.point_losses(p2, p3, label=y, weight=w, dual=dual)
+        seen = {}
+        for k in L:   # the stream that is current while a leaf receives its gradient is the one its loss node was created on
+            L[k].register_hook(lambda g, k=k: seen.__setitem__(k, torch.cuda.current_stream().cuda_stream))
+        loss2, loss3 = res.ce_2d + 0.1 * res.kl_2d, res.ce_3d + 0.1 * res.kl_3d
+        loss2.backward()
+        if use_dual:
+            dual.backward_on_side(loss3)
+            dual.join()
+        else:
+            loss3.backward()
+        assert torch.cuda.current_stream().cuda_stream == main
+        side = dual.side.cuda_stream if use_dual else main
+        assert use_dual == (side != main)
+        assert rec.names[-3:] == ["mopa_point_losses_fwd", "mopa_point_losses_bwd", "mopa_point_losses_bwd"]
+        assert rec.streams[-3:] == [main, main, side]
+        for k in L:
+            assert seen[k] == (side if k.startswith("z3") else main), k
+        runs[use_dual] = [res.ce_2d, res.kl_2d, res.ce_3d, res.kl_3d] + [L[k].grad for k in sorted(L)]
+        monkeypatch.undo()
+    torch.cuda.synchronize()
+    for a, b in zip(runs[False], runs[True]):
+        assert torch.equal(a, b) and _same_bits(a, b)
+
+
+def test_no_rows_and_label_validation(monkeypatch):
+    from mopa_amd import trainloss
+    from mopa_amd.common.utils import loss as single
+    from mopa_amd.models.metric import SegIoU
+    rec = _Recorder(monkeypatch, trainloss)
+    z2, z3 = torch.zeros(0, 5, device="cuda", requires_grad=True), torch.zeros(0, 5, device="cuda", requires_grad=True)
+    m = SegIoU(5)
+    res = trainloss.point_losses({"seg_logit": z2}, {"seg_logit": z3}, label=torch.zeros(0, dtype=torch.int64, device="cuda"), metric_2d=m)
+    assert rec.names == [] and m.mat is None
+    for t in (res.ce_2d, res.kl_2d, res.ce_3d, res.kl_3d):
+        assert t.dim() == 0 and torch.isnan(t) and t.requires_grad
+    N, C = 63, 5
+    c = _case(N, C)
+    bad = c["y"].clone()
+    bad[5] = C
+    p = ({"seg_logit": c["z2m"].cuda()}, {"seg_logit": c["z3m"].cuda()})
+    assert trainloss.point_losses(*p, label=bad.cuda()).status.item() == 1     # flagged, not raised
+    monkeypatch.setattr(single, "VALIDATE_LABELS", True)
+    with pytest.raises(IndexError):
+        trainloss.point_losses(*p, label=bad.cuda())
+    assert trainloss.point_losses(*p, label=c["y"].cuda()).status.item() == 0
+    with pytest.raises(ValueError):
+        trainloss.point_losses(*p, label=c["y"].cuda(), metric_3d=SegIoU(C + 1))
+
+
+# ------------------------------------------------------------------------------------------------ refusals
+def test_refused_calls_write_nothing():
+    lib = _lib()
+    N = 300
+    rng = torch.Generator().manual_seed(3)
+
+    def outputs(C):
+        return {"scalars": torch.full((8,), SENTINEL, device="cuda"), "conf": torch.full((2, C, C), 77, dtype=torch.int64, device="cuda"),
+                "acc": torch.full((2,), 77, dtype=torch.int64, device="cuda"), "status": torch.full((1,), 4, dtype=torch.int32, device="cuda"),
+                "dz": torch.full((2, N, C), SENTINEL, device="cuda")}
+
+    def untouched(o):
+        torch.cuda.synchronize()
+        return ((o["scalars"] == SENTINEL).all() and (o["conf"] == 77).all() and (o["acc"] == 77).all() and (o["status"] == 4).all()
+                and (o["dz"] == SENTINEL).all())
+
+    def fwd(C, o, ws, ws_bytes):
+        z = torch.randn(2, N, C, generator=rng).cuda()
+        y = torch.zeros(N, dtype=torch.int64, device="cuda")
+        mask = torch.ones(N, dtype=torch.uint8, device="cuda")
+        lib.call("mopa_point_losses_fwd", lib.ptr(z[0]), lib.ptr(z[0]), lib.ptr(z[1]), lib.ptr(z[1]), lib.ptr(y), lib.ptr(y), None, N, C, -100,
+                 lib.ptr(o["scalars"]), lib.ptr(o["conf"][0]), lib.ptr(o["conf"][1]), lib.ptr(mask), lib.ptr(o["acc"]), lib.ptr(o["status"]),
+                 lib.ptr(ws), ws_bytes, lib.stream())
+
+    need = lib.query("mopa_point_losses_workspace_bytes", N)
+    assert need >= 6 * 2048 * 8
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    o = outputs(MAXC + 1)
+    with pytest.raises(RuntimeError, match=r"mopa_point_losses_fwd failed with code -1$"):     # MOPA_ERR_ARG
+        fwd(MAXC + 1, o, ws, need)
+    assert untouched(o)
+    o = outputs(5)
+    with pytest.raises(RuntimeError, match=r"mopa_point_losses_fwd failed with code -2$"):     # MOPA_ERR_WORKSPACE
+        fwd(5, o, ws, need - 1)
+    assert untouched(o)
+    fwd(5, o, ws, need)                                                                        # ... and the exact size is taken
+    torch.cuda.synchronize()
+    assert not untouched(o) and o["acc"].tolist() == [77 + int(o["conf"][1][0, 0]) - 77, 77 + N]
+
+    C = 5
+    o = outputs(C)
+    z = torch.randn(2, N, C, generator=rng).cuda()
+    y = torch.zeros(N, dtype=torch.int64, device="cuda")
+    den, g = torch.ones(1, device="cuda"), torch.ones(2, device="cuda")
+
+    def bwd(C, z_xm, dz_xm):
+        lib.call("mopa_point_losses_bwd", lib.ptr(z[0]), z_xm, lib.ptr(z[1]), lib.ptr(y), None, N, C, -100, lib.ptr(den), lib.ptr(g),
+                 lib.ptr(o["dz"][0]), dz_xm, lib.stream())
+
+    for args in ((C, lib.ptr(z[0]), lib.ptr(o["dz"][1])),          # a shared head with two gradient buffers
+                 (C, lib.ptr(z[1]), lib.ptr(o["dz"][0])),          # two heads with one gradient buffer
+                 (MAXC + 1, lib.ptr(z[0]), lib.ptr(o["dz"][0]))):
+        with pytest.raises(RuntimeError, match=r"mopa_point_losses_bwd failed with code -1$"):
+            bwd(*args)
+        assert untouched(o)
