@@ -23,15 +23,17 @@ enum { OP_KIND = 0, OP_CKIND, OP_LSRC, OP_LDST, OP_SBUF, OP_SCOL, OP_SC, OP_DBUF
 enum { K_BN = 0, K_CONV = 1, K_ADD = 2 };
 enum { C_SUBM = 0, C_DOWN = 1, C_UP = 2, C_NIN = 3 };
 // params_host int64 [n_ops][4]: BatchNorm gamma, beta, running_mean, running_var | convolution weight [K][Cin][Cout], -, -, -
-// forms_host  int64 [n_ops][2][3]: per convolution and pass (0 forward, 1 backward-data): buffer (K*Cin*Cout floats), column-group
-//             width the buffer was packed for (0 = plain per-offset transpose, -1 = never built), weight epoch it was built at
+// forms_host  int64 [n_ops][2][3]: per convolution and pass (0 forward, 1 backward-data): buffer (K*Cin*Cout floats), the form the
+//             buffer holds (the form part of mopa_spconv_plan: 0 = plain per-offset transpose; -1 = never built), weight epoch it was built at
 // geom_host   int64: [0] levels L, [1] n_points, [2] point_row, [3] row_start, [4] row_points, [5] grp_o, [6] grp_in, [7] grp_out,
 //             then per level l at 8 + 8 l: rows A_l, nbr27, its grp_start, ch (rows A_{l+1}), its grp_start, up (rows A_l), its grp_start,
 //             split_l (0: one BatchNorm group; s: rows [0, s) and [s, A_l) are groups of scans whose BatchNorm statistics, running
 //             updates and gradients are computed separately, first group first -- mopa_amd/sparse3d.py::Geometry3D.split);
 //             behind the L + 1 level rows: a tail of 8 values, tail[l] = second split of level l (0: none) -- three groups;
 //             behind the tail: 3 values per level l (up to 8 levels), the run-major rulebooks (sprun.hip) of nbr27 / ch / up at that
-//             level, 0 = none built (the offset-major path then does not run on that table)
+//             level, 0 = none built (the offset-major path then does not run on that table);
+//             behind those: 8 values, one per level l: bit 0 / 1 / 2 = every output row of nbr27 / ch / up at that level has exactly
+//             one rule (the deconvolution tables: every fine row has one parent)
 enum { G_L = 0, G_NPTS, G_PROW, G_RSTART, G_RPTS, G_GO, G_GI, G_GOUT, G_LEVELS = 8, G_LW = 8 };
 enum { GL_A = 0, GL_NBR, GL_NBR_GS, GL_CH, GL_CH_GS, GL_UP, GL_UP_GS, GL_SPLIT };
 // bufs_host   int64 [nbufs][2]: base pointer, row stride (floats) of the activation (or gradient) buffers
@@ -90,63 +92,103 @@ struct Table { const int32_t* nbr; const int32_t* gs; int K; int rows_out; const
 static inline const int32_t* runs_of(const int64_t* geom, int l, int which) {   // which: 0 nbr27, 1 ch, 2 up
   return (const int32_t*)geom[G_LEVELS + G_LW * ((int)geom[G_L] + 1) + 8 + 3 * l + which];
 }
+static inline int one_of(const int64_t* geom, int l, int which) {
+  return (int)(geom[G_LEVELS + G_LW * ((int)geom[G_L] + 1) + 8 + 24 + l] >> which) & 1;
+}
 // the rule table a convolution of `ckind` between levels runs on (forward), or its reverse (backward-data)
 static inline Table table_of(const int64_t* geom, int ckind, int l, bool reversed) {
   const int64_t* g = geom + G_LEVELS + G_LW * l;
   Table t;
   const int A_l = (int)g[GL_A], A_c = (int)g[G_LW + GL_A];   // (A_c is only read for down / up, where level l + 1 exists)
   t.runs = nullptr; t.one = 0;
-  if (ckind == C_SUBM) { t.nbr = (const int32_t*)g[GL_NBR]; t.gs = (const int32_t*)g[GL_NBR_GS]; t.K = 27; t.rows_out = A_l; t.runs = runs_of(geom, l, 0); }
+  if (ckind == C_SUBM) { t.nbr = (const int32_t*)g[GL_NBR]; t.gs = (const int32_t*)g[GL_NBR_GS]; t.K = 27; t.rows_out = A_l; t.runs = runs_of(geom, l, 0); t.one = one_of(geom, l, 0); }
   else if (ckind == C_NIN) { t.nbr = (const int32_t*)g[GL_NBR] + (int64_t)13 * A_l; t.gs = nullptr; t.K = 1; t.rows_out = A_l; }
-  else if ((ckind == C_DOWN) != reversed) { t.nbr = (const int32_t*)g[GL_CH]; t.gs = (const int32_t*)g[GL_CH_GS]; t.K = 8; t.rows_out = A_c; t.runs = runs_of(geom, l, 1); }
-  else { t.nbr = (const int32_t*)g[GL_UP]; t.gs = (const int32_t*)g[GL_UP_GS]; t.K = 8; t.rows_out = A_l; t.runs = runs_of(geom, l, 2); t.one = 1; }   // every fine row has one parent
+  else if ((ckind == C_DOWN) != reversed) { t.nbr = (const int32_t*)g[GL_CH]; t.gs = (const int32_t*)g[GL_CH_GS]; t.K = 8; t.rows_out = A_c; t.runs = runs_of(geom, l, 1); t.one = one_of(geom, l, 1); }
+  else { t.nbr = (const int32_t*)g[GL_UP]; t.gs = (const int32_t*)g[GL_UP_GS]; t.K = 8; t.rows_out = A_l; t.runs = runs_of(geom, l, 2); t.one = one_of(geom, l, 2); }
   return t;
 }
 
-// Which weight form the convolution kernel of (table, cin -> cout) wants: > 0 packed for column groups of that many 16-column
-// tiles, 0 = the plain [K][cin][cout] weight of the convolution to run, SCN_RUN_FORM + nt = the run layout of the offset-major
-// kernel (sprun.hip; nt = its column-group width).  Mirrors mopa_amd/sparse3d.py::spconv_fwd.
-#define SCN_RUN_FORM 100
-static inline int wanted_ntw(const Table& t, int cin, int cout, int ld_in) {
-  if ((int64_t)t.rows_out * 8 * ld_in * 4 >= (1ll << 32)) return 0;
-  if (t.runs && mopa_spconv_run_wanted(t.K, t.rows_out, cin, cout, t.one)) return SCN_RUN_FORM + mopa_spconv_run_form(cin, cout);
-  if (!t.gs) return 0;
-  return mopa_spconv_grouped_wants_packed(t.K, t.rows_out, cin, cout);
+// ---- The plan of one sparse convolution: the ONE place where the measured leaf rules (mopa_spconv_run_wanted, mopa_spconv_run_form,
+// mopa_spconv_grouped_wants_packed: sprun.hip / spconv.hip) are composed into the kernel a convolution runs as and the weight form
+// that kernel reads.  Both walks of the layer program ask it: this file and mopa_amd/sparse3d.py::spconv_fwd.
+//   K, num_out: the table to run on; cin, cout: of the convolution to run (swapped for backward-data); ld_in: row stride of its input;
+//   has_grouped / has_runs: the table has a grouped / a run-major rulebook; one_rule_per_row: the table's fact (geom_host).
+//   -> path << 24 | form.  path: 0 the dense table (mopa_spconv_fwd), 1 the block kernel on the grouped rulebook with the
+//   offset-split workspace (mopa_spconv_fwd_grouped), 2 the pipelined kernels on packed weights (mopa_spconv_fwd_grouped, w_flip
+//   bit 1), 3 offset-major (mopa_spconv_fwd_run).  form: the flags word of mopa_spconv_pack_weights_batched without its transpose
+//   bit -- column-group width << 8, 0x10000 for the run layout; 0 = the plain [K][cin][cout] weight of the convolution to run.
+enum { SP_DENSE = 0, SP_BLOCK = 1, SP_PACKED = 2, SP_RUN = 3 };
+#define PLAN_PATH(p) ((p) >> 24)
+#define PLAN_FORM(p) ((p) & 0xffffff)
+MOPA_API int mopa_spconv_plan(int32_t K, int32_t num_out, int32_t cin, int32_t cout, int32_t ld_in, int32_t has_grouped, int32_t has_runs,
+                              int32_t one_rule_per_row) {
+  // the pipelined and the offset-major kernels address the input rows with 32-bit byte offsets (an input has at most 8x the output's rows)
+  const bool narrow = (int64_t)num_out * 8 * ld_in * 4 < (1ll << 32);
+  if (narrow && has_runs && mopa_spconv_run_wanted(K, num_out, cin, cout, one_rule_per_row))
+    return (SP_RUN << 24) | 0x10000 | (mopa_spconv_run_form(cin, cout) << 8);
+  const int ntw = narrow && has_grouped ? mopa_spconv_grouped_wants_packed(K, num_out, cin, cout) : 0;
+  if (ntw > 0) return (SP_PACKED << 24) | (ntw << 8);
+  // measured on MI355X (profiles/bench_spconv.py): where the pipelined kernels do not take a shape, the 4-wave block kernel with
+  // LDS-staged weights wins on the short levels (27-offset tables below 1,500 tiles, the 8-offset down / up tables below 200), the
+  // dense-table wave kernel elsewhere (<= 4 input channels: the stem kernel inside mopa_spconv_fwd)
+  if (has_grouped && cin > 4 && cdiv64(num_out, 64) < (K == 27 ? 1500 : 200)) return SP_BLOCK << 24;
+  return SP_DENSE << 24;
+}
+// scratch the launch of `plan` needs: the offset-split partial outputs of the block kernel, the slab of the offset-major kernel
+// (none when every output row has one rule: products go straight to the output)
+MOPA_API size_t mopa_spconv_plan_workspace_bytes(int32_t plan, int32_t K, int32_t num_out, int32_t cout, int32_t one_rule_per_row) {
+  if (PLAN_PATH(plan) == SP_BLOCK) return mopa_spconv_grouped_workspace_bytes(K, num_out, cout);
+  if (PLAN_PATH(plan) == SP_RUN && !one_rule_per_row) return mopa_spconv_run_workspace_bytes(K, num_out, cout);
+  return 0;
+}
+static inline int plan_of(const Table& t, int cin, int cout, int ld_in) {
+  return mopa_spconv_plan(t.K, t.rows_out, cin, cout, ld_in, t.gs != nullptr, t.runs != nullptr, t.one);
 }
 
-// The weight gradient of a convolution of `ckind` at level l: on the run lists where sprun.hip's dispatcher wants them -- the
-// table's own run-major rulebook, or (stride-2 convolution: its forward table has none) the deconvolution table's with the two index
-// lists swapped -- else on the dense table.  Mirrors mopa_amd/sparse3d.py::spconv_bwd_weight_of.
-struct WgradPlan { Table t; int run; int swap; };
+// ---- The plan of one weight gradient (composes mopa_spconv_wgrad_run_wanted; asked by this file and sparse3d.py::spconv_bwd_weight_of).
+//   ckind: 0 submanifold, 1 stride-2 convolution, 2 deconvolution, 3 NetworkInNetwork; K, num_out, has_runs, one_rule_per_row: the
+//   convolution's own table; deconv_*: for the stride-2 convolution, the deconvolution table between the same levels (the same
+//   (coarse, fine, offset) triples); cin, cout: of the layer.
+//   -> 0 the dense table (mopa_spconv_bwd_weight), 1 the run lists of the own table, 2 the run lists of the deconvolution table
+//   with the two index lists swapped (mopa_spconv_bwd_weight_run) -- only a table with one rule per row can be read that way.
+enum { WG_DENSE = 0, WG_RUN = 1, WG_RUN_SWAPPED = 2 };
+MOPA_API int mopa_spconv_wgrad_plan(int32_t ckind, int32_t K, int32_t num_out, int32_t has_runs, int32_t one_rule_per_row, int32_t deconv_num_out,
+                                    int32_t deconv_has_runs, int32_t deconv_one_rule_per_row, int32_t cin, int32_t cout) {
+  if (ckind == C_NIN) return WG_DENSE;
+  if (has_runs) return mopa_spconv_wgrad_run_wanted(K, num_out, cin, cout, one_rule_per_row) ? WG_RUN : WG_DENSE;
+  if (ckind == C_DOWN && deconv_has_runs && deconv_one_rule_per_row && mopa_spconv_wgrad_run_wanted(K, deconv_num_out, cin, cout, 1))
+    return WG_RUN_SWAPPED;
+  return WG_DENSE;
+}
+// scratch of the launch `wplan` names (num_out, one_rule_per_row: of the table it runs on)
+MOPA_API size_t mopa_spconv_wgrad_plan_workspace_bytes(int32_t wplan, int32_t K, int32_t num_out, int32_t cin, int32_t cout, int32_t one_rule_per_row) {
+  return wplan == WG_DENSE ? mopa_spconv_wgrad_workspace_bytes(K, num_out, cin, cout)
+                           : mopa_spconv_wgrad_run_workspace_bytes(K, num_out, cin, cout, one_rule_per_row);
+}
+struct WgradPlan { Table t; int plan; };   // t: the table the launch reads
 static inline WgradPlan wgrad_plan_of(const int64_t* geom, int ckind, int l, int cin, int cout) {
+  const Table t = table_of(geom, ckind, l, false);
+  Table r = t;
+  if (ckind == C_DOWN) r = table_of(geom, ckind, l, true);
   WgradPlan w;
-  w.t = table_of(geom, ckind, l, false);
-  w.run = 0; w.swap = 0;
-  if (ckind == C_NIN) return w;
-  if (w.t.runs) {
-    w.run = mopa_spconv_wgrad_run_wanted(w.t.K, w.t.rows_out, cin, cout, w.t.one);
-    return w;
-  }
-  if (ckind == C_DOWN) {
-    const Table r = table_of(geom, ckind, l, true);   // the deconvolution table: the same (coarse, fine, offset) triples
-    if (r.runs && r.one && mopa_spconv_wgrad_run_wanted(r.K, r.rows_out, cin, cout, 1)) { w.t = r; w.run = 1; w.swap = 1; }
-  }
+  w.plan = mopa_spconv_wgrad_plan(ckind, t.K, t.rows_out, t.runs != nullptr, t.one, r.rows_out, r.runs != nullptr, r.one, cin, cout);
+  w.t = w.plan == WG_RUN_SWAPPED ? r : t;
   return w;
 }
 static inline size_t wgrad_workspace(const WgradPlan& w, int cin, int cout) {
-  return w.run ? mopa_spconv_wgrad_run_workspace_bytes(w.t.K, w.t.rows_out, cin, cout, w.t.one)
-               : mopa_spconv_wgrad_workspace_bytes(w.t.K, w.t.rows_out, cin, cout);
+  return mopa_spconv_wgrad_plan_workspace_bytes(w.plan, w.t.K, w.t.rows_out, cin, cout, w.t.one);
 }
 static inline int run_wgrad(const WgradPlan& w, const View& x, const View& dy, float* dw, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (w.run)
-    return mopa_spconv_bwd_weight_run(w.t.runs, w.t.K, w.t.rows_out, w.t.one, w.swap, x.p, x.ld, x.C, dy.p, dy.ld, dy.C, dw, accumulate, ws, ws_bytes, st);
+  if (w.plan != WG_DENSE)
+    return mopa_spconv_bwd_weight_run(w.t.runs, w.t.K, w.t.rows_out, w.t.one, w.plan == WG_RUN_SWAPPED, x.p, x.ld, x.C, dy.p, dy.ld, dy.C, dw,
+                                      accumulate, ws, ws_bytes, st);
   return mopa_spconv_bwd_weight(w.t.nbr, w.t.K, w.t.rows_out, x.p, x.ld, x.C, dy.p, dy.ld, dy.C, dw, accumulate, ws, ws_bytes, st);
 }
 
-// Make the weight form of (op, pass) valid for `ntw` at `epoch`; returns the pointer the kernel reads.  pass 0: forward
-// (ntw 0 = the parameter itself), pass 1: backward-data (the convolution to run is the per-offset transpose).
-static const float* form_ptr(const int64_t* params, int64_t* forms, int op, int pass, int ntw) {
-  if (pass == 0 && ntw == 0) return reinterpret_cast<const float*>(params[op * 4]);
+// The pointer the kernel of `plan` reads for (op, pass).  pass 0: forward (form 0 = the parameter itself), pass 1: backward-data
+// (the convolution to run is the per-offset transpose).
+static const float* form_ptr(const int64_t* params, int64_t* forms, int op, int pass, int plan) {
+  if (pass == 0 && PLAN_FORM(plan) == 0) return reinterpret_cast<const float*>(params[op * 4]);
   return reinterpret_cast<const float*>(forms[(op * 2 + pass) * 3]);
 }
 
@@ -175,38 +217,37 @@ static int refresh_forms(const int32_t* prog, int n_ops, const int64_t* params, 
     const int cin_w = o[OP_SC], cout_w = o[OP_DC];                 // the layer weight is [K][cin_w][cout_w]
     const int cin = pass == 0 ? cin_w : cout_w, cout = pass == 0 ? cout_w : cin_w;
     const int ld_in = pass == 0 ? (int)bufs[o[OP_SBUF] * 2 + 1] : (int)gbufs[plan[i * PL_W + PL_DYBUF] * 2 + 1];
-    const int ntw = wanted_ntw(t, cin, cout, ld_in);
-    if (pass == 0 && ntw == 0) continue;                           // forward on the parameter itself
+    const int form = PLAN_FORM(plan_of(t, cin, cout, ld_in));
+    if (pass == 0 && form == 0) continue;                          // forward on the parameter itself
     int64_t* f = forms + (op * 2 + pass) * 3;
-    if (f[1] == ntw && f[2] == epoch) continue;
+    if (f[1] == form && f[2] == epoch) continue;
     if (!f[0]) return MOPA_ERR_ARG;
     int64_t* r = rows + n * 6;
     r[0] = params[op * 4]; r[1] = f[0]; r[2] = t.K; r[3] = cin_w; r[4] = cout_w;
-    if (ntw >= SCN_RUN_FORM) r[5] = (pass == 1 ? 1 : 0) | ((ntw - SCN_RUN_FORM) << 8) | 0x10000;   // the run layout
-    else r[5] = ntw > 0 ? ((pass == 1 ? 1 : 0) | (ntw << 8)) : 1;  // ntw 0 (backward-data only): plain per-offset transpose
-    f[1] = ntw; f[2] = epoch;
+    r[5] = form | (pass == 1 ? 1 : 0);                             // form 0 (backward-data only): plain per-offset transpose
+    f[1] = form; f[2] = epoch;
     if (++n == 64) { const int rc = flush(); if (rc) return rc; }
   }
   return flush();
 }
 
-// out = conv(x) on table t with the weight form the plan asks for
-static int run_conv(const Table& t, const View& x, const float* wk, int ntw, const View& out, int w_flip, const int64_t* geom, void* ws,
+// out = conv(x) on table t as `plan` says, on the weight form it names
+static int run_conv(const Table& t, const View& x, const float* wk, int plan, const View& out, int w_flip, const int64_t* geom, void* ws,
                     size_t ws_bytes, hipStream_t st) {
   const int32_t* go = (const int32_t*)geom[G_GO];
   const int32_t* gi = (const int32_t*)geom[G_GI];
   const int32_t* gout = (const int32_t*)geom[G_GOUT];
-  const int64_t tiles = cdiv64(t.rows_out, 64);
-  if (ntw >= SCN_RUN_FORM)
-    return mopa_spconv_fwd_run(t.runs, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip, out.p, out.ld, t.one, ws, ws_bytes, st);
-  if (ntw > 0)
-    return mopa_spconv_fwd_grouped(t.gs, go, gi, gout, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip | 2, out.p, out.ld, nullptr, 0, st);
-  if (t.gs && x.C > 4 && tiles < (t.K == 27 ? 1500 : 200)) {   // (<= 4 input channels: the stem kernel inside mopa_spconv_fwd)
-    const size_t need = mopa_spconv_grouped_workspace_bytes(t.K, t.rows_out, out.C);
-    return mopa_spconv_fwd_grouped(t.gs, go, gi, gout, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip, out.p, out.ld, ws,
-                                   ws_bytes >= need ? ws_bytes : 0, st);
+  switch (PLAN_PATH(plan)) {
+    case SP_RUN:
+      return mopa_spconv_fwd_run(t.runs, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip, out.p, out.ld, t.one, ws, ws_bytes, st);
+    case SP_PACKED:
+      return mopa_spconv_fwd_grouped(t.gs, go, gi, gout, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip | 2, out.p, out.ld, nullptr, 0, st);
+    case SP_BLOCK:
+      return mopa_spconv_fwd_grouped(t.gs, go, gi, gout, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip, out.p, out.ld, ws,
+                                     ws_bytes >= mopa_spconv_plan_workspace_bytes(plan, t.K, t.rows_out, out.C, t.one) ? ws_bytes : 0, st);
+    default:
+      return mopa_spconv_fwd(t.nbr, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip, out.p, out.ld, st);
   }
-  return mopa_spconv_fwd(t.nbr, t.K, t.rows_out, x.p, x.ld, x.C, wk, out.C, w_flip, out.p, out.ld, st);
 }
 
 static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
@@ -223,11 +264,10 @@ MOPA_API size_t mopa_scn_workspace_bytes(const int32_t* prog_host, int32_t n_ops
       const int l = o[OP_LSRC] < o[OP_LDST] ? o[OP_LSRC] : o[OP_LDST];
       for (int rev = 0; rev < 2; ++rev) {
         const Table t = table_of(geom_host, o[OP_CKIND], l, rev);
-        const int cout = rev ? o[OP_SC] : o[OP_DC];
-        need = max_sz(need, mopa_spconv_grouped_workspace_bytes(t.K, t.rows_out, cout));
-        const int cin = rev ? o[OP_DC] : o[OP_SC];
-        if (t.runs && !t.one && mopa_spconv_run_wanted(t.K, t.rows_out, cin, cout, 0))
-          need = max_sz(need, mopa_spconv_run_workspace_bytes(t.K, t.rows_out, cout));
+        const int cin = rev ? o[OP_DC] : o[OP_SC], cout = rev ? o[OP_SC] : o[OP_DC];
+        // the input's row stride is not known here; it only decides the 32-bit-offset guard of the plan: both sides of it
+        for (int ld_in : {cin, 1 << 27})
+          need = max_sz(need, mopa_spconv_plan_workspace_bytes(plan_of(t, cin, cout, ld_in), t.K, t.rows_out, cout, t.one));
       }
       need = max_sz(need, wgrad_workspace(wgrad_plan_of(geom_host, o[OP_CKIND], l, o[OP_SC], o[OP_DC]), o[OP_SC], o[OP_DC]));
     }
@@ -269,8 +309,8 @@ MOPA_API int mopa_scn_forward(const int32_t* prog_host, int32_t n_ops, const int
     } else if (o[OP_KIND] == K_CONV) {
       const int l = o[OP_LSRC] < o[OP_LDST] ? o[OP_LSRC] : o[OP_LDST];
       const Table t = table_of(geom_host, o[OP_CKIND], l, false);
-      const int ntw = wanted_ntw(t, src.C, dst.C, src.ld);
-      rc = run_conv(t, src, form_ptr(params_host, forms_host, i, 0, ntw), ntw, dst, 0, geom_host, ws, ws_bytes, st);
+      const int plan = plan_of(t, src.C, dst.C, src.ld);
+      rc = run_conv(t, src, form_ptr(params_host, forms_host, i, 0, plan), plan, dst, 0, geom_host, ws, ws_bytes, st);
     } else {
       const View b = view_of(bufs_host, geom_host, o[OP_ABUF], o[OP_ACOL], o[OP_DC], o[OP_LDST]);
       rc = mopa_rows_add(src.p, src.ld, b.p, b.ld, dst.p, dst.ld, dst.rows, dst.C, st);
@@ -354,8 +394,8 @@ MOPA_API int mopa_scn_backward(const int32_t* prog_host, int32_t n_ops, const in
     // backward-data: the same kernel on the reversed rules with the per-offset transposed weight (submanifold: the table is its own
     // reverse with mirrored offsets; stride-2 convolution <-> deconvolution swap tables)
     const Table tr = table_of(geom_host, ck, l, true);
-    const int ntw = wanted_ntw(tr, dy.C, dx.C, dy.ld);
-    rc = run_conv(tr, dy, form_ptr(params_host, forms_host, op, 1, ntw), ntw, dx, ck == C_SUBM ? 1 : 0, geom_host, ws, ws_bytes, st);
+    const int plan = plan_of(tr, dy.C, dx.C, dy.ld);
+    rc = run_conv(tr, dy, form_ptr(params_host, forms_host, op, 1, plan), plan, dx, ck == C_SUBM ? 1 : 0, geom_host, ws, ws_bytes, st);
     if (rc) break;
   }
   if (side && (hipEventRecord(ev_done, wst) != hipSuccess || hipStreamWaitEvent(st, ev_done, 0) != hipSuccess)) return MOPA_ERR_LAUNCH;

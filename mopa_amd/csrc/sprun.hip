@@ -351,8 +351,12 @@ __global__ __launch_bounds__(256) void k_run_reduce(const int* __restrict__ pos,
 //   * the 8-offset tables with several rules per row (Convolution k2s2 forward, Deconvolution backward-data): within 10 % either
 //     way on every level -- they stay on the output-stationary kernels.
 // MOPA_SPCONV_RUN=0 switches the path off, =2 forces it wherever the shape is supported (tuning / tests).
-MOPA_API int mopa_spconv_run_wanted(int32_t K, int32_t num_out, int32_t cin, int32_t cout, int32_t one_rule_per_row) {
+static int run_mode() {
   static const int mode = getenv("MOPA_SPCONV_RUN") ? atoi(getenv("MOPA_SPCONV_RUN")) : 1;
+  return mode;
+}
+MOPA_API int mopa_spconv_run_wanted(int32_t K, int32_t num_out, int32_t cin, int32_t cout, int32_t one_rule_per_row) {
+  const int mode = run_mode();
   const int64_t rows_per = 110000;
   if (mode == 0 || K <= 0 || K > 27 || num_out <= 0 || run_nt(cin, cout) == 0) return 0;
   if ((int64_t)num_out * 8 * 224 * 4 >= (1ll << 32)) return 0;   // 32-bit byte offsets into the input rows
@@ -363,6 +367,15 @@ MOPA_API int mopa_spconv_run_wanted(int32_t K, int32_t num_out, int32_t cin, int
   // exceeds 1 GiB (the measured wins all sit below 0.8 GiB) -- they stay on the output-stationary kernels
   if (run_cap(K, num_out) * (int64_t)cout * (int64_t)sizeof(float) > (1ll << 30)) return 0;
   return cin >= 64 && cout >= 48 && (int64_t)num_out * cout <= rows_per * cin;
+}
+
+// Which tables get a run-major rulebook at all (the geometry builder asks once per table; a table without one never takes the
+// offset-major path, whatever mopa_spconv_run_wanted says): every table with one rule per output row (the deconvolution tables:
+// products go straight to the output) and the 27-offset tables up to 220,000 rows (above, the partial slab's bytes cost more than
+// the fuller MFMA groups return) -- never the stride-2 convolution tables, nothing with MOPA_SPCONV_RUN=0.
+MOPA_API int mopa_rulebook_runs_wanted(int32_t K, int32_t num_out, int32_t one_rule_per_row) {
+  if (run_mode() == 0 || K <= 0 || K > 27 || num_out <= 0) return 0;
+  return one_rule_per_row || (K == 27 && num_out <= 220000);
 }
 
 // Column-group width of the run layout for the convolution cin -> cout (0: shape not supported): what the batched weight-form

@@ -25,8 +25,20 @@ BN_EPS = 1e-4       # SCN BatchNormalization eps (Appendix A.6)
 BN_MOMENTUM = 0.1   # SCN "momentum 0.9" == torch-style 0.1
 LEAK = 0.0          # scn.UNet leakiness=0 / BatchNormReLU
 BATCHED_REPACK = True   # one launch for all stale weight forms (the single-form path stays for never-built forms; tests flip the attribute)
-RUN_PATH = os.environ.get("MOPA_SPCONV_RUN", "1") != "0"             # the offset-major convolution (csrc/sprun.hip); 0 = round-4 kernels only
-RUN_MAX_ROWS = 220000   # 27-offset tables above this get no run-major rulebook
+PATH_DENSE, PATH_BLOCK, PATH_PACKED, PATH_RUN = range(4)   # mopa_spconv_plan (csrc/scn_exec.hip)
+WGRAD_DENSE, WGRAD_RUN, WGRAD_RUN_SWAPPED = range(3)       # mopa_spconv_wgrad_plan
+# 1 = every output row of such a table has exactly one rule (the deconvolution tables: every fine row has one parent)
+ONE_RULE_PER_ROW = dict(nbr27=0, ch=0, up=1)
+
+
+def plan_parts(plan: int):
+    """A word of mopa_spconv_plan -> (path, weight form: the flags word of mopa_spconv_pack_weights_batched without its transpose bit)."""
+    return plan >> 24, plan & 0xffffff
+
+
+def plan_of_path(path: int) -> int:
+    """The plan word of a launch whose path is known (what mopa_spconv_plan_workspace_bytes reads of it)."""
+    return path << 24
 
 
 def _pow2_at_least(n):
@@ -147,17 +159,17 @@ class Geometry3D:
         for i, t in enumerate(tables):
             self._rb[t.data_ptr()] = (gs[tile0[i]:tile0[i + 1] + 1], go, gi, gout)
         # run-major rulebooks (csrc/sprun.hip: the rules of one filter offset as one contiguous run of slots) for the tables the
-        # offset-major convolution can take -- every deconvolution table (one rule per output row: products go straight to the
-        # output) and the 27-offset tables up to RUN_MAX_ROWS rows (above, the partial slab's bytes cost more than the fuller MFMA
-        # groups return: mopa_spconv_run_wanted) -- all in three launches, sized from the bound K * rows (no host round trip)
-        self._runs = {}
-        rt = [t for t in self.up] + [t for t in self.nbr27 if t.shape[1] <= RUN_MAX_ROWS] if RUN_PATH else []
+        # offset-major convolution can take (mopa_rulebook_runs_wanted) -- all in three launches, sized from the bound K * rows (no
+        # host round trip)
+        self._runs = {}   # table -> (run-major rulebook, the table's one-rule-per-row fact)
+        rt = [(t, one) for name in ("up", "nbr27", "ch") for t in getattr(self, name) for one in (ONE_RULE_PER_ROW[name],)
+              if query("mopa_rulebook_runs_wanted", *t.shape, one)]
         for i in range(0, len(rt), 24):
             rows = []
-            for t in rt[i:i + 24]:
+            for t, one in rt[i:i + 24]:
                 K, Ao = t.shape
                 buf = torch.empty(query("mopa_rulebook_runs_bytes", K, Ao) // 4, **i32)
-                self._runs[t.data_ptr()] = buf
+                self._runs[t.data_ptr()] = (buf, one)
                 rows.append((t.data_ptr(), K, Ao, buf.data_ptr()))
             rdesc = np.asarray(rows, dtype=np.int64)
             call("mopa_rulebook_runs_build_batched", rdesc.ctypes.data, len(rows), st)
@@ -173,7 +185,7 @@ class Geometry3D:
         d = getattr(self, "_desc", None)
         if d is None:
             L = self.num_levels
-            d = np.zeros(8 + 8 * (L + 1) + 8 + 24, np.int64)   # header, L + 1 level rows, tail (second group boundary per level), run rulebooks
+            d = np.zeros(8 + 8 * (L + 1) + 8 + 24 + 8, np.int64)   # header, L + 1 level rows, tail (second group boundary per level), run rulebooks, one-rule-per-row bits
             gs0, go, gi, gout = self._rb[self.nbr27[0].data_ptr()]
             d[0:8] = (L, self.n_points, self.point_row.data_ptr(), self.row_start.data_ptr(), self.row_points.data_ptr(),
                       go.data_ptr(), gi.data_ptr(), gout.data_ptr())
@@ -184,9 +196,9 @@ class Geometry3D:
                     r[3], r[4] = self.ch[l].data_ptr(), self._rb[self.ch[l].data_ptr()][0].data_ptr()
                     r[5], r[6] = self.up[l].data_ptr(), self._rb[self.up[l].data_ptr()][0].data_ptr()
                 rbase = 8 + 8 * (L + 1) + 8 + 3 * l
-                d[rbase] = self._run_ptr(self.nbr27[l])
-                if l < L - 1:
-                    d[rbase + 1], d[rbase + 2] = self._run_ptr(self.ch[l]), self._run_ptr(self.up[l])
+                for i, name in enumerate(("nbr27", "ch", "up") if l < L - 1 else ("nbr27",)):
+                    d[rbase + i] = self._run_ptr(getattr(self, name)[l])
+                    d[8 + 8 * (L + 1) + 8 + 24 + l] |= ONE_RULE_PER_ROW[name] << i
                 if self.split is not None:
                     r[7] = self.split[l][0]
                     if len(self.split[l]) > 1:
@@ -211,14 +223,11 @@ class Geometry3D:
     def runs(self, table: torch.Tensor):
         """(run-major rulebook of the table, 1 if every output row has exactly one rule -- the deconvolution tables -- else 0),
         or None when none was built."""
-        buf = self._runs.get(table.data_ptr())
-        if buf is None:
-            return None
-        return buf, int(any(table is u for u in self.up))
+        return self._runs.get(table.data_ptr())
 
     def _run_ptr(self, table):
-        buf = self._runs.get(table.data_ptr())
-        return 0 if buf is None else buf.data_ptr()
+        r = self._runs.get(table.data_ptr())
+        return 0 if r is None else r[0].data_ptr()
 
     def tensors(self):
         """Every device tensor this geometry owns."""
@@ -227,7 +236,7 @@ class Geometry3D:
             out += list(lst)
         for rb in self._rb.values():
             out += list(rb)
-        out += list(self._runs.values())
+        out += [buf for buf, _ in self._runs.values()]
         return out
 
     def record_stream(self, stream):
@@ -283,20 +292,14 @@ def spconv_fwd(nbr: torch.Tensor, x: View, w: torch.Tensor, out: View, w_flip: b
     K, A_out = nbr.shape
     cin, cout = x.C, out.C
     assert out.rows == A_out and w.shape == ((K, cout, cin) if w_transposed else (K, cin, cout)), (nbr.shape, cin, cout, w.shape)
-    if runs is not None and A_out * 8 * x.ld * 4 < 1 << 32 and query("mopa_spconv_run_wanted", K, A_out, cin, cout, runs[1]):
-        # offset-major: per-offset GEMM into a partial slab + ordered per-row sum (csrc/sprun.hip); same rule as scn_exec.hip
-        wk = _weight_form(w, ("run", int(w_transposed), query("mopa_spconv_run_form", cin, cout)))
+    plan = query("mopa_spconv_plan", K, A_out, cin, cout, x.ld, int(rb is not None), int(runs is not None), runs[1] if runs is not None else 0)
+    path, form = plan_parts(plan)
+    flags = form | int(w_transposed)
+    wk = _weight_form(w, flags) if flags else w
+    if path == PATH_RUN:
         spconv_launch_run(runs, K, x, wk, out, w_flip)
-        return
-    ntw = query("mopa_spconv_grouped_wants_packed", K, A_out, cin, cout) if rb is not None else 0
-    if A_out * 8 * x.ld * 4 >= 1 << 32:   # the pipelined kernels use 32-bit byte offsets into the input rows
-        ntw = 0
-    packed = ntw > 0
-    if packed:   # column groups of ntw 16-column tiles, MFMA-operand order (mopa_spconv_pack_weight)
-        wk = _weight_form(w, ("pack", int(w_transposed), ntw))
     else:
-        wk = _weight_form(w, ("transpose",)) if w_transposed else w
-    spconv_launch(nbr, x, wk, out, w_flip, rb, packed)
+        spconv_launch(nbr, x, wk, out, w_flip, None if path == PATH_DENSE else rb, path == PATH_PACKED)
 
 
 _weight_cache = {}
@@ -323,9 +326,7 @@ def _refresh_stale_forms(st):
         new_tag = (epoch, w._version, w.data_ptr())
         if tag == new_tag:
             continue
-        form = key[1]
-        flags = (form[1] | (form[2] << 8)) if form[0] == "pack" else (form[1] | (form[2] << 8) | 0x10000) if form[0] == "run" else 1
-        rows.append((w.data_ptr(), t.data_ptr(), w.shape[0], w.shape[1], w.shape[2], flags))
+        rows.append((w.data_ptr(), t.data_ptr(), w.shape[0], w.shape[1], w.shape[2], key[1]))
         hits.append((key, new_tag, t, wref))
     for i in range(0, len(rows), 64):
         desc = np.asarray(rows[i:i + 64], dtype=np.int64)
@@ -334,13 +335,14 @@ def _refresh_stale_forms(st):
         cache[key] = (new_tag, t, wref)
 
 
-def _weight_form(w: torch.Tensor, form: tuple) -> torch.Tensor:
-    """Packed / transposed form of a conv weight, re-used until the weight changes (the source and the target half of an
+def _weight_form(w: torch.Tensor, flags: int) -> torch.Tensor:
+    """Packed / transposed form of a conv weight -- `flags`: the form the plan named | the transpose bit, the flags word of
+    mopa_spconv_pack_weights_batched -- re-used until the weight changes (the source and the target half of an
     iteration share the weights).  Same validity rules as dense2d.relayout_cached: one live tensor object, one weight
     version (autograd counter + _lib.WEIGHTS_EPOCH), one stream."""
     import weakref
     st = stream()
-    key = (id(w), form, st)
+    key = (id(w), flags, st)
     scope = _lib.FORM_SCOPE   # (mopa_amd.teacher: the forms of the EMA weights live in the teacher's own dictionaries)
     cache, refreshed = (_weight_cache, _refreshed) if scope is None else (scope.forms3d, scope.refreshed3d)
     tag = (_lib.weights_epoch(), w._version, w.data_ptr())
@@ -354,12 +356,12 @@ def _weight_form(w: torch.Tensor, form: tuple) -> torch.Tensor:
         if hit is not None and hit[0] == tag:
             return hit[1]
     K = w.shape[0]
-    if form[0] == "pack":
+    if flags & 0x10000:        # the one-form kernels of the same layouts
         t = torch.empty(w.numel(), dtype=w.dtype, device=w.device)
-        call("mopa_spconv_pack_weight", ptr(w), K, w.shape[1], w.shape[2], form[1], form[2], ptr(t), stream())
-    elif form[0] == "run":
+        call("mopa_spconv_run_pack_weight", ptr(w), K, w.shape[1], w.shape[2], flags & 1, ptr(t), stream())
+    elif flags >> 8:
         t = torch.empty(w.numel(), dtype=w.dtype, device=w.device)
-        call("mopa_spconv_run_pack_weight", ptr(w), K, w.shape[1], w.shape[2], form[1], ptr(t), stream())
+        call("mopa_spconv_pack_weight", ptr(w), K, w.shape[1], w.shape[2], flags & 1, flags >> 8, ptr(t), stream())
     else:
         t = spconv_transpose_weight(w)
     if len(cache) > 4096:
@@ -369,19 +371,18 @@ def _weight_form(w: torch.Tensor, form: tuple) -> torch.Tensor:
 
 
 def spconv_launch(nbr: torch.Tensor, x: View, wk: torch.Tensor, out: View, w_flip: bool, rb, packed: bool):
-    """The convolution launch itself, on a weight already laid out for the kernel that runs (bench.py times this)."""
+    """The convolution launch itself, on a weight already laid out for the kernel that runs (bench.py times this): `packed` = the
+    pipelined kernels on the grouped rulebook `rb`, else `rb` = the block kernel on it with its offset-split workspace, else the
+    dense table.  Which of them a convolution takes: mopa_spconv_plan."""
     K, A_out = nbr.shape
     cin, cout = x.C, out.C
-    # measured on MI355X (profiles/bench_spconv.py): 27-offset tables run the pipelined kernels on packed weights (one wave
-    # per tile at 16 channels, four waves per tile and column group above); the 8-offset down/up tables the dense-table
-    # wave kernel, except on the shortest levels (< 200 tiles) where the 4-wave block kernel with LDS-staged weights wins.
     if packed:
         gs, go, gi, gout = rb
         call("mopa_spconv_fwd_grouped", ptr(gs), ptr(go), ptr(gi), ptr(gout), K, A_out, x.p, x.ld, cin, ptr(wk), cout,
              int(w_flip) | 2, out.p, out.ld, 0, 0, stream())
-    elif rb is not None and cin > 4 and (A_out + 63) // 64 < (1500 if K == 27 else 200):   # (<= 4 input channels: the stem kernel inside mopa_spconv_fwd)
+    elif rb is not None:
         gs, go, gi, gout = rb
-        ws = workspace.get(query("mopa_spconv_grouped_workspace_bytes", K, A_out, cout), wk.device)
+        ws = workspace.get(query("mopa_spconv_plan_workspace_bytes", plan_of_path(PATH_BLOCK), K, A_out, cout, 0), wk.device)
         call("mopa_spconv_fwd_grouped", ptr(gs), ptr(go), ptr(gi), ptr(gout), K, A_out, x.p, x.ld, cin, ptr(wk), cout,
              int(w_flip), out.p, out.ld, ptr(ws), ws.numel(), stream())
     else:
@@ -391,7 +392,8 @@ def spconv_launch(nbr: torch.Tensor, x: View, wk: torch.Tensor, out: View, w_fli
 def spconv_launch_run(runs, K: int, x: View, wk: torch.Tensor, out: View, w_flip: bool):
     """The offset-major convolution launch (gather-GEMM + ordered reduce) on a weight in the run layout (bench.py times this)."""
     buf, one = runs
-    ws = None if one else workspace.get(query("mopa_spconv_run_workspace_bytes", K, out.rows, out.C), wk.device)
+    wsb = query("mopa_spconv_plan_workspace_bytes", plan_of_path(PATH_RUN), K, out.rows, out.C, one)
+    ws = workspace.get(wsb, wk.device) if wsb else None
     call("mopa_spconv_fwd_run", ptr(buf), K, out.rows, x.p, x.ld, x.C, ptr(wk), out.C, int(w_flip), out.p, out.ld, one,
          ptr(ws), 0 if ws is None else ws.numel(), stream())
 
@@ -413,28 +415,22 @@ def spconv_bwd_weight(nbr: torch.Tensor, x: View, dout: View, dw: torch.Tensor, 
 
 
 def spconv_bwd_weight_of(geom, kind: str, l: int, x: View, dout: View, dw: torch.Tensor, accumulate: bool = False):
-    """The weight gradient of the convolution (kind, level l): on the run-major rulebook where csrc/sprun.hip's dispatcher wants it
-    (mopa_spconv_wgrad_run_wanted) -- the table's own, or for the stride-2 convolution the deconvolution table's with the two index
-    lists swapped -- else on the dense table.  Mirrors csrc/scn_exec.hip::wgrad_plan_of (the two paths give the same bits)."""
+    """The weight gradient of the convolution (kind, level l) as mopa_spconv_wgrad_plan says: on the dense table, on the table's own
+    run-major rulebook, or -- the stride-2 convolution -- on the deconvolution table's with the two index lists swapped (the paths
+    give the same bits)."""
     t = geom.rule_table(kind, l)
-    if kind != "nin":
-        rt, swap = (t, 0)
-        r = geom.runs(rt)
-        if r is None and kind == "down":
-            rt, swap = geom.up[l], 1
-            r = geom.runs(rt)
-            if r is not None and not r[1]:
-                r = None
-        if r is not None:
-            buf, one = r
-            K, A = rt.shape
-            if query("mopa_spconv_wgrad_run_wanted", K, A, x.C, dout.C, one):
-                assert dw.shape == (K, x.C, dout.C)
-                ws = workspace.get(query("mopa_spconv_wgrad_run_workspace_bytes", K, A, x.C, dout.C, one), dw.device)
-                call("mopa_spconv_bwd_weight_run", ptr(buf), K, A, one, swap, x.p, x.ld, x.C, dout.p, dout.ld, dout.C, ptr(dw),
-                     int(accumulate), ptr(ws), ws.numel(), stream())
-                return
-    spconv_bwd_weight(t, x, dout, dw, accumulate=accumulate)
+    d = geom.up[l] if kind == "down" else t   # (only the stride-2 convolution has another table to read)
+    r, rd = geom.runs(t), geom.runs(d)
+    plan = query("mopa_spconv_wgrad_plan", ("subm", "down", "up", "nin").index(kind), *t.shape, int(r is not None), r[1] if r else 0,
+                 d.shape[1], int(rd is not None), rd[1] if rd else 0, x.C, dout.C)
+    if plan == WGRAD_DENSE:
+        return spconv_bwd_weight(t, x, dout, dw, accumulate=accumulate)
+    rt, (buf, one) = (d, rd) if plan == WGRAD_RUN_SWAPPED else (t, r)
+    K, A = rt.shape
+    assert dw.shape == (K, x.C, dout.C)
+    ws = workspace.get(query("mopa_spconv_wgrad_plan_workspace_bytes", plan, K, A, x.C, dout.C, one), dw.device)
+    call("mopa_spconv_bwd_weight_run", ptr(buf), K, A, one, int(plan == WGRAD_RUN_SWAPPED), x.p, x.ld, x.C, dout.p, dout.ld, dout.C, ptr(dw),
+         int(accumulate), ptr(ws), ws.numel(), stream())
 
 
 def bn_row_groups(geom, level: int):

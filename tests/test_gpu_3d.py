@@ -330,9 +330,9 @@ def test_weight_gradient_on_the_run_lists_tiny_geometries(n, batch):
 
 
 def test_weight_gradient_dispatch_native_executor_equals_python_walk(monkeypatch):
-    """The native executor (csrc/scn_exec.hip::wgrad_plan_of) and the Python walk (sparse3d.spconv_bwd_weight_of) choose the weight
-    gradient's kernel per layer by the same rule (mopa_spconv_wgrad_run_wanted: here the 64- to 192-channel 27-offset layers take the
-    run lists, the rest the dense table) and give the same bits for every parameter gradient."""
+    """The native executor (csrc/scn_exec.hip) and the Python walk (sparse3d.spconv_fwd / spconv_bwd_weight_of) ask the same plan per
+    layer (mopa_spconv_plan, mopa_spconv_wgrad_plan: here the 64- to 192-channel 27-offset layers take the run lists for the weight
+    gradient, the rest the dense table) and give the same bits for the three outputs, every parameter gradient and d(feats)."""
     from mopa_amd import sparse3d as s3, synth
     from mopa_amd.config import default_cfg
     from mopa_amd.models.build import build_model_3d
@@ -345,19 +345,84 @@ def test_weight_gradient_dispatch_native_executor_equals_python_walk(monkeypatch
         monkeypatch.setattr(s3, "NATIVE", native)
         torch.manual_seed(3)
         m = build_model_3d(default_cfg())[0].cuda().train()
-        out = m(batch)
+        feats = batch["x"][1].cuda().requires_grad_()
+        out = m(dict(batch, x=[batch["x"][0], feats]))
         g = torch.Generator(device="cuda").manual_seed(5)
         (out["seg_logit"] * torch.randn(out["seg_logit"].shape, device="cuda", generator=g)).sum().backward()
         torch.cuda.synchronize()
-        return {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+        assert feats.grad is not None and sorted(out) == ["feats", "seg_logit", "seg_logit2"]
+        got = {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
+        got.update({"out/" + k: v.detach().clone() for k, v in out.items()})
+        got["d(feats)"] = feats.grad.clone()
+        return got
 
     ga = run(True)
     n0 = calls.count("mopa_spconv_bwd_weight_run")
     gb = run(False)
     assert n0 == 0   # (native: one C-ABI call per pass)
     assert calls.count("mopa_spconv_bwd_weight_run") >= 5 and calls.count("mopa_spconv_bwd_weight") >= 10
+    assert sorted(ga) == sorted(gb)
     for n in ga:
         assert torch.equal(ga[n], gb[n]), n
+
+
+def test_the_python_walk_launches_what_the_plan_names_vs_oracle(monkeypatch):
+    """sparse3d.spconv_fwd and spconv_bwd_weight_of launch the entry point mopa_spconv_plan / mopa_spconv_wgrad_plan name -- every
+    forward path (dense table, block kernel with its offset-split workspace, pipelined kernels on packed weights, offset-major with
+    and without the slab) and every weight-gradient outcome this geometry reaches -- and the result is the fp64 oracle's
+    (oracle/scn3d.py::sparse_conv).  20,000 points: the smallest cloud of this generator with a deconvolution table of 8,192 rows, from
+    where the one-rule-per-row offset-major rule takes it."""
+    from mopa_amd import sparse3d as s3
+    from mopa_amd._lib import query
+    c = _cloud(21, n=20000)
+    g, o = _geoms(c, 2, 64)
+    A0, A1 = o.num_active
+    assert (A0, A1) == (15347, 6130)
+    dev = "cuda"
+    calls = []
+    inner = s3.call
+    monkeypatch.setattr(s3, "call", lambda name, *a: (calls.append((name, a)), inner(name, *a))[1])
+    rng = np.random.Generator(np.random.PCG64(21))
+    DENSE, BLOCK, PACKED, RUN = range(4)
+    entry = {DENSE: "mopa_spconv_fwd", BLOCK: "mopa_spconv_fwd_grouped", PACKED: "mopa_spconv_fwd_grouped", RUN: "mopa_spconv_fwd_run"}
+    for tab_g, tab_o, A_in, cin, cout, path in ((g.nbr27[0], o.nbr27[0], A0, 1, 16, DENSE), (g.ch[0], o.ch[0], A0, 32, 16, BLOCK),
+                                                (g.nbr27[0], o.nbr27[0], A0, 64, 32, PACKED), (g.nbr27[0], o.nbr27[0], A0, 64, 64, RUN),
+                                                (g.up[0], o.up[0], A1, 32, 16, RUN), (g.up[0], o.up[0], A1, 16, 16, DENSE)):
+        K, A_out = tab_o.shape
+        x = torch.from_numpy(rng.standard_normal((A_in, cin), dtype=np.float32))
+        w = torch.from_numpy(rng.standard_normal((K, cin, cout), dtype=np.float32) * 0.2)
+        ref = scn3d.sparse_conv(x.double(), tab_o, w.double())
+        rb, runs = g.rulebook(tab_g), g.runs(tab_g)
+        assert rb is not None and (runs is not None) == (K == 27 or tab_g is g.up[0])
+        one = runs[1] if runs is not None else 0
+        plan = query("mopa_spconv_plan", K, A_out, cin, cout, cin, 1, int(runs is not None), one)
+        assert s3.plan_parts(plan)[0] == path, (K, cin, cout, plan)
+        xv, ov = s3.View(x.to(dev)), s3.new_view(A_out, cout, dev)
+        del calls[:]
+        s3.spconv_fwd(tab_g, xv, w.to(dev), ov, rb=rb, runs=runs)
+        launches = [(n, a) for n, a in calls if n in entry.values()]
+        assert len(launches) == 1 and launches[0][0] == entry[path], (K, cin, cout, [n for n, _ in calls])
+        a = launches[0][1]
+        if path in (BLOCK, PACKED):     # w_flip bit 1 = packed weights; the block kernel gets its offset-split workspace
+            assert bool(a[11] & 2) == (path == PACKED) and bool(a[14]) == (path == BLOCK)
+        if path == RUN:                 # the slab, unless every output row has one rule
+            assert a[11] == one and bool(a[12]) == (not one)
+        scale = max(1.0, float(ref.abs().max()))
+        np.testing.assert_allclose(ov.dense().cpu().numpy(), ref.float().numpy(), rtol=1e-4, atol=2e-5 * scale, err_msg=f"{K} {cin}->{cout}")
+    for kind, tab_o, A_in, cin, cout, wplan in (("subm", o.nbr27[0], A0, 64, 64, 1), ("down", o.ch[0], A0, 16, 32, 0),
+                                               ("nin", o.nbr27[0][13:14], A0, 16, 32, 0)):
+        K, A_out = tab_o.shape
+        x = torch.from_numpy(rng.standard_normal((A_in, cin), dtype=np.float32))
+        gout = torch.from_numpy(rng.standard_normal((A_out, cout), dtype=np.float32))
+        wr = torch.zeros(K, cin, cout, dtype=torch.float64, requires_grad=True)
+        (scn3d.sparse_conv(x.double(), tab_o, wr) * gout.double()).sum().backward()
+        dw = torch.empty(K, cin, cout, device=dev)
+        del calls[:]
+        s3.spconv_bwd_weight_of(g, kind, 0, s3.View(x.to(dev)), s3.View(gout.to(dev)), dw)
+        names = [n for n, _ in calls if n.startswith("mopa_spconv_bwd_weight")]
+        assert names == ["mopa_spconv_bwd_weight_run" if wplan else "mopa_spconv_bwd_weight"], (kind, names)
+        sw = max(1.0, float(wr.grad.abs().max()))
+        np.testing.assert_allclose(dw.cpu().numpy(), wr.grad.float().numpy(), rtol=2e-4, atol=5e-5 * sw, err_msg=kind)
 
 
 def test_dispatcher_sends_the_matrix_bound_layers_to_the_offset_major_kernel():
