@@ -355,7 +355,9 @@ __device__ __forceinline__ int table_lookup(const uint64_t* __restrict__ tk, con
 // The table is point-symmetric -- nbr[o][i] = j  <=>  nbr[26 - o][j] = i -- so only offsets 0 .. 12 are probed (13 random hash
 // probes per row instead of 26: the probes were 7x the kernel's algorithmic bytes, a 64-byte sector per 8-byte key); a hit also
 // writes the mirrored entry, rows 14 .. 26 are pre-filled with -1 (every entry is written by at most one thread: the mirror of
-// (o, i) is unique).  Same table bit for bit.
+// (o, i) is unique).  Same table bit for bit -- for rows INSIDE the field: every x, y, z of row_keys must be < spatial_size (the
+// range test looks at the neighbour, not at the row it starts from, so a row outside would be found from inside by the mirrored
+// write, which the specification does not do).  Geometry3D refuses such coordinates before it builds a table.
 __global__ __launch_bounds__(256) void k_rulebook_subm(const uint64_t* __restrict__ row_keys, int A,
                                                         const uint64_t* __restrict__ tk, const int* __restrict__ tv,
                                                         uint32_t mask, int size, int* __restrict__ nbr) {
@@ -384,6 +386,8 @@ __global__ __launch_bounds__(256) void k_rulebook_subm(const uint64_t* __restric
 
 __global__ void k_fill_i32(int* __restrict__ p, int64_t n, int v);
 
+// row_keys[num_rows] with every x, y, z inside [0, spatial_size) (the caller's contract, not checked here) and the table built
+// from them -> nbr[27][num_rows].
 MOPA_API int mopa_rulebook_subm(const uint64_t* row_keys, int32_t num_rows, const uint64_t* table_keys,
                                 const int32_t* table_vals, int64_t table_cap, int32_t spatial_size,
                                 int32_t* nbr /*[27][num_rows]*/, void* stream) {

@@ -107,10 +107,18 @@ class Geometry3D:
             # the groups must not share a voxel (scan indices disjoint and increasing from group to group: merge_domains_3d offsets
             # them): then every row of the points behind the boundary is a NEW row.  Checked on the device, read back with the rest.
             meta[L] += 2 * (item_row[0][b:N].min() < meta[base]).to(torch.int32)
+        if full_scale < 4096:
+            # a voxel outside the field: mopa_rulebook_subm range-checks the neighbour it looks for, not the row it starts from, and
+            # mirrors every hit -- its table would disagree with the specification (oracle.scn3d.Geometry).  At 4096 the key range
+            # IS the field and k_pack_keys has set bit 0 already: the training path gains no launch here.  Bit 3: the boundary
+            # checks above add up to 4.
+            meta[L] += 8 * (coords[:, :3].max() >= full_scale).to(torch.int32)
         m = meta.cpu().tolist()  # the one host sync of the geometry build
         if m[L] & 1:
             raise RuntimeError("voxel coordinates out of range: need 0 <= x,y,z < 4096 and batch >= 0")
-        if m[L] > 1:
+        if m[L] & 8:
+            raise RuntimeError(f"voxel coordinates outside the field: need x,y,z < full_scale = {full_scale}")
+        if m[L] & 6:
             raise ValueError("group_points: a point behind a group boundary falls into a voxel of the group in front of it -- the groups' scan "
                              "indices (coords[:, 3]) must be disjoint and increasing from group to group (mopa_amd.step.merge_domains_3d)")
         self.num_active = m[:L]

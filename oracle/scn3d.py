@@ -78,6 +78,10 @@ class Geometry:
             coords = np.concatenate([coords, np.zeros((len(coords), 1), np.int64)], 1)   # mopa/models/xmuda_arch.py:171 calls it so)
         self.n_points = coords.shape[0]
         self.num_levels = num_levels
+        # every voxel lies inside the field: one outside would still see its in-range neighbours while they do not see it (the
+        # range test below looks at the neighbour only) -- a table that is not point-symmetric.  The reference's loader drops such
+        # points (nuscenes_dataloader.py:419-424); Geometry3D refuses them.
+        assert (coords[:, :3] < full_scale).all(), "voxel coordinates must lie inside [0, full_scale)"
         keys = pack_keys(coords)
         row_keys, self.point_row = first_seen_unique(keys)
         self.point_row = self.point_row.astype(np.int32)

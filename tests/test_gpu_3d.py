@@ -76,6 +76,16 @@ def test_geometry_rejects_out_of_range():
         Geometry3D(torch.from_numpy(c), 2, 4096, "cuda")
     with pytest.raises(RuntimeError):
         Geometry3D(torch.zeros(0, 4, dtype=torch.int64), 2, 4096, "cuda")
+    # a voxel outside a field smaller than the key range: x, y, z < 4096, but not < full_scale
+    c = _cloud(3)
+    Geometry3D(torch.from_numpy(c), 2, 64, "cuda")
+    for axis in range(3):
+        c = _cloud(3)
+        c[5, axis] = 64
+        with pytest.raises(RuntimeError, match="full_scale"):
+            Geometry3D(torch.from_numpy(c), 2, 64, "cuda")
+    c[5, 2] = 63
+    Geometry3D(torch.from_numpy(c), 2, 64, "cuda")
 
 
 @pytest.mark.parametrize("cin,cout", [(1, 16), (16, 16), (32, 16), (48, 48), (64, 32), (80, 96), (192, 96), (96, 112),
