@@ -412,6 +412,427 @@ MOPA_API int mopa_point_losses_bwd(const float* z_main, const float* z_xm, const
   return MOPA_OK;
 }
 
+// ------------------------------------------------------------------------------------------ the same block over row segments
+// The loss block of a MERGED pass (source, target and the VGI batch as row segments of one logit tensor per network; bn_groups /
+// bn_group_points upstream): all segments of an iteration in one forward launch pair and one backward launch per network, and
+// entropy minimisation (mopa/models/losses.py:21-34 on the softmax of the main head, train_xmuda.py:323-330) as a third
+// per-segment term.  A block serves exactly one segment and reduces it as k_point_losses reduces a call of N = n_s rows:
+// g_s = stream_grid(n_s, 256) virtual blocks, the same row walk, the same device functions and block_sum_d order, partials
+// [S][PL_SEG_TERMS][g_s] -- so every CE / KL scalar and every gradient row without an entropy part has the bits of the
+// per-slice call (tests/test_gpu_trainloss_merged.py).  A network's rows are the concatenation, in segment order, of the segments
+// it takes part in.
+#define PL_MAXSEG 8
+#define PL_SEG_TERMS 8   // per-block partials of a segment: CE numerator, CE normaliser, KL sum, entropy sum of the 2D, then the 3D network
+#define PL_SEG_KL 1
+#define PL_SEG_WEIGHTED 2
+#define PL_SEG_MINENT 4
+#define PL_LN2 0.6931471805599453f
+
+// One entry of the host-side descriptor table `segs_host` (ten 64-bit words per segment).
+struct PointLossSeg {
+  int64_t n;                 // rows
+  int64_t row0[2];           // first row in the 2D / 3D logits, -1: the network takes no part in this segment
+  const int64_t* y[2];       // (n,) labels per network, or null: no CE and no confusion matrix
+  const uint8_t* acc_mask;   // (n,) or null
+  int64_t* conf[2];          // (C, C) int64, ADDED to; or null
+  int64_t* acc_out;          // [2], ADDED to; or null
+  int64_t flags;             // PL_SEG_KL | PL_SEG_WEIGHTED | PL_SEG_MINENT
+};
+static_assert(sizeof(PointLossSeg) == 80, "segs_host is ten 64-bit words per segment");
+
+struct PointLossSegArgs {
+  PointLossSeg seg[PL_MAXSEG];
+  int blk0[PL_MAXSEG + 1];   // first block of every segment; blk0[S] = the grid
+  const float* zm[2];        // merged main-head logits of the 2D / 3D network, or null
+  const float* zx[2];        // merged logits of the head the KL term trains (== zm without a dual head), or null: no KL
+  const float* w;
+  int64_t ignore;
+  int S, C;
+  double* partial;           // segment s: PL_SEG_TERMS * blk0[s] + [PL_SEG_TERMS][g_s]
+  int* status;
+};
+
+// the segment a block serves: the last one that starts at or before it (a zero-row segment owns no block)
+__device__ __forceinline__ int seg_of_block(const int* blk0, int S) {
+  int s = 0;
+  for (int j = 1; j < S; ++j) s = (int)blockIdx.x >= blk0[j] ? j : s;
+  return s;
+}
+
+// one row's sum_c p_c log2(p_c + 1e-30), p = exp(z - lse)
+__device__ __forceinline__ float ent_row(const float* __restrict__ zr, float l, int C) {
+  float e = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float p = expf(zr[c] - l);
+    e += p * log2f(p + 1e-30f);
+  }
+  return e;
+}
+// d(p log2(p + 1e-30))/dp
+__device__ __forceinline__ float ent_slope(float p) { return log2f(p + 1e-30f) + p / ((p + 1e-30f) * PL_LN2); }
+
+__global__ __launch_bounds__(LOSS_BLOCK) void k_point_losses_seg(PointLossSegArgs a) {
+  extern __shared__ int pl_hist[];   // [#matrices][C][C]
+  __shared__ double lds[8];
+  __shared__ int pl_acc[2];
+  const int s = seg_of_block(a.blk0, a.S);
+  const PointLossSeg& sg = a.seg[s];
+  const int vb = blockIdx.x - a.blk0[s], g = a.blk0[s + 1] - a.blk0[s], N = (int)sg.n;
+  const int C = a.C, CC = C * C;
+  const int flags = (int)sg.flags;
+  const float* zm[2];
+  const float* zx[2];
+  bool ce[2], kl[2], ent[2], shared[2];
+  int64_t* conf[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const bool in = sg.row0[k] >= 0;
+    zm[k] = in ? a.zm[k] + sg.row0[k] * C : nullptr;
+    zx[k] = in && a.zx[k] ? a.zx[k] + sg.row0[k] * C : nullptr;
+    ce[k] = in && sg.y[k];
+    ent[k] = in && (flags & PL_SEG_MINENT);
+    shared[k] = a.zx[k] == a.zm[k];
+    conf[k] = ce[k] ? sg.conf[k] : nullptr;
+  }
+  const bool both = (flags & PL_SEG_KL) && zm[0] && zm[1];
+  kl[0] = both && zx[0];
+  kl[1] = both && zx[1];
+  const float* w = (flags & PL_SEG_WEIGHTED) ? a.w : nullptr;
+  const uint8_t* acc_mask = ce[1] ? sg.acc_mask : nullptr;
+
+  int* hist[2] = {conf[0] ? pl_hist : nullptr, conf[1] ? pl_hist + (conf[0] ? CC : 0) : nullptr};
+  const int nh = ((conf[0] ? 1 : 0) + (conf[1] ? 1 : 0)) * CC;
+  for (int b = threadIdx.x; b < nh; b += blockDim.x) pl_hist[b] = 0;
+  if (threadIdx.x < 2) pl_acc[threadIdx.x] = 0;
+  __syncthreads();
+
+  double num[2] = {0.0, 0.0}, den[2] = {0.0, 0.0}, ksum[2] = {0.0, 0.0}, esum[2] = {0.0, 0.0};
+  int hit = 0, seen = 0;
+  for (int i = vb * blockDim.x + threadIdx.x; i < N; i += g * blockDim.x) {
+    int64_t yi[2] = {0, 0};
+    bool keep[2] = {false, false};
+    float lm[2] = {0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (ce[k]) {
+        yi[k] = sg.y[k][i];
+        if (yi[k] != a.ignore) {
+          if (yi[k] < 0 || yi[k] >= C) atomicOr(a.status, 1);
+          else keep[k] = true;
+        }
+      }
+      if (keep[k] || kl[1 - k] || (kl[k] && shared[k]) || ent[k]) lm[k] = row_lse(zm[k] + (int64_t)i * C, C);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const float* zr = zm[k] + (int64_t)i * C;
+      if (keep[k]) {
+        const float wi = w ? w[yi[k]] : 1.f;
+        num[k] += (double)(wi * (lm[k] - zr[yi[k]]));
+        den[k] += (double)wi;
+      }
+      if (kl[k]) {
+        const float* ar = zx[k] + (int64_t)i * C;
+        const float la = shared[k] ? lm[k] : row_lse(ar, C);
+        ksum[k] += (double)kl_row(ar, la, zm[1 - k] + (int64_t)i * C, lm[1 - k], C);
+      }
+      if (ent[k]) esum[k] += (double)ent_row(zr, lm[k], C);
+      const bool masked = k == 1 && acc_mask && acc_mask[i];
+      if ((hist[k] && keep[k]) || masked) {
+        const int arg = row_argmax(zr, C);
+        if (hist[k] && keep[k]) atomicAdd(&hist[k][(int)yi[k] * C + arg], 1);
+        if (masked) { seen += 1; hit += (int64_t)arg == yi[k] ? 1 : 0; }
+      }
+    }
+  }
+  if (acc_mask) {
+    hit = wave_sum_i(hit);
+    seen = wave_sum_i(seen);
+    if ((threadIdx.x & 63) == 0 && seen) { atomicAdd(&pl_acc[0], hit); atomicAdd(&pl_acc[1], seen); }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < nh; b += blockDim.x) {
+    int64_t* dst = b < CC && conf[0] ? conf[0] + b : conf[1] + (b - (conf[0] ? CC : 0));
+    if (pl_hist[b]) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)pl_hist[b]);
+  }
+  if (acc_mask && threadIdx.x < 2 && pl_acc[threadIdx.x])
+    atomicAdd(reinterpret_cast<unsigned long long*>(sg.acc_out + threadIdx.x), (unsigned long long)pl_acc[threadIdx.x]);
+  double* part = a.partial + (size_t)PL_SEG_TERMS * a.blk0[s] + vb;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    if (ce[k]) {
+      const double sn = block_sum_d(num[k], lds);
+      const double sd = block_sum_d(den[k], lds);
+      if (threadIdx.x == 0) { part[(size_t)(4 * k) * g] = sn; part[(size_t)(4 * k + 1) * g] = sd; }
+    }
+    if (kl[k]) {
+      const double sk = block_sum_d(ksum[k], lds);
+      if (threadIdx.x == 0) part[(size_t)(4 * k + 2) * g] = sk;
+    }
+    if (ent[k]) {
+      const double se = block_sum_d(esum[k], lds);
+      if (threadIdx.x == 0) part[(size_t)(4 * k + 3) * g] = se;
+    }
+  }
+}
+
+struct PointLossSegFin {
+  int blk0[PL_MAXSEG + 1];
+  int has[PL_MAXSEG];        // bit 4k / 4k+1 / 4k+2: CE / KL / entropy term of network k
+  double kl_scale[PL_MAXSEG];    // 1 / n_s
+  double ent_scale[PL_MAXSEG];   // -1 / (n_s log2 C)
+  const double* partial;
+  float* scalars;            // [S][2][4]: ce, den, kl, ent
+};
+
+// One block per segment: k_point_losses_finalize's sums over the segment's g_s partials.
+__global__ void k_point_losses_seg_finalize(PointLossSegFin f) {
+  __shared__ double lds[8];
+  const int s = blockIdx.x, n = f.blk0[s + 1] - f.blk0[s], has = f.has[s];
+  const double* base = f.partial + (size_t)PL_SEG_TERMS * f.blk0[s];
+  float* out = f.scalars + 8 * s;
+  for (int k = 0; k < 2; ++k) {
+    if (has >> (4 * k) & 1) {
+      const double* p = base + (size_t)(4 * k) * n;
+      double a = 0.0, b = 0.0;
+      for (int i = threadIdx.x; i < n; i += blockDim.x) { a += p[i]; b += p[n + i]; }
+      const double sn = block_sum_d(a, lds);
+      const double sd = block_sum_d(b, lds);
+      if (threadIdx.x == 0) { out[4 * k] = (float)(sn / sd); out[4 * k + 1] = (float)sd; }
+    }
+    if (has >> (4 * k + 1) & 1) {
+      const double* p = base + (size_t)(4 * k + 2) * n;
+      double acc = 0.0;
+      for (int i = threadIdx.x; i < n; i += blockDim.x) acc += p[i];
+      const double sk = block_sum_d(acc, lds);
+      if (threadIdx.x == 0) out[4 * k + 2] = (float)(sk * f.kl_scale[s]);
+    }
+    if (has >> (4 * k + 2) & 1) {
+      const double* p = base + (size_t)(4 * k + 3) * n;
+      double acc = 0.0;
+      for (int i = threadIdx.x; i < n; i += blockDim.x) acc += p[i];
+      const double se = block_sum_d(acc, lds);
+      if (threadIdx.x == 0) out[4 * k + 3] = (float)(se * f.ent_scale[s]);
+    }
+  }
+}
+
+struct PointLossSegBwdArgs {
+  PointLossSeg seg[PL_MAXSEG];
+  int blk0[PL_MAXSEG + 1];   // over the segments this network takes part in
+  const float* z_main;
+  const float* z_xm;
+  const float* z_other;
+  const float* w;
+  int64_t ignore;
+  int S, C, net;
+  float log2c;
+  const float* scalars;
+  const float* g;            // [S][3]: upstream gradients of (ce, kl, ent)
+  float* dz_main;
+  float* dz_xm;
+};
+
+// One network's gradients over all of its rows: per segment k_point_losses_bwd's expressions with gce = g_ce / den_s and
+// gkl = g_kl / n_s, zeros where the segment has no term for a head, and the entropy part
+//   -g_ent / (n_s log2 C) * p_c * (t_c - sum_i p_i t_i),  t = ent_slope(p)
+// added to dz_main after the CE / KL parts (add_parts: no multiply is contracted into either add).
+__global__ __launch_bounds__(LOSS_BLOCK) void k_point_losses_seg_bwd(PointLossSegBwdArgs a) {
+  const int s = seg_of_block(a.blk0, a.S);
+  const PointLossSeg& sg = a.seg[s];
+  const int vb = blockIdx.x - a.blk0[s], gb = a.blk0[s + 1] - a.blk0[s], N = (int)sg.n;
+  const int C = a.C, k = a.net, flags = (int)sg.flags;
+  const int64_t* y = sg.y[k];
+  const float* w = (flags & PL_SEG_WEIGHTED) ? a.w : nullptr;
+  const bool ce = y != nullptr;
+  const bool kl = (flags & PL_SEG_KL) && sg.row0[1 - k] >= 0 && a.z_xm && a.z_other;
+  const bool ent = flags & PL_SEG_MINENT;
+  const bool one_head = !a.z_xm || a.z_xm == a.z_main;   // dz_main is the only output
+  const bool shared = kl && one_head;
+  const float* gs = a.g + 3 * s;
+  const float gce = ce ? gs[0] / a.scalars[8 * s + 4 * k + 1] : 0.f;
+  const float gkl = kl ? gs[1] / (float)N : 0.f;
+  const float gent = ent ? -gs[2] / ((float)N * a.log2c) : 0.f;
+  const float* z_main = a.z_main + sg.row0[k] * C;
+  const float* z_xm = kl ? a.z_xm + sg.row0[k] * C : nullptr;
+  const float* z_other = kl ? a.z_other + sg.row0[1 - k] * C : nullptr;
+  float* dz_main = a.dz_main + sg.row0[k] * C;
+  float* dz_xm = one_head ? nullptr : a.dz_xm + sg.row0[k] * C;
+  for (int i = vb * blockDim.x + threadIdx.x; i < N; i += gb * blockDim.x) {
+    int64_t yi = 0;
+    bool keep = false;
+    if (ce) {
+      yi = y[i];
+      keep = !(yi == a.ignore || yi < 0 || yi >= C);
+    }
+    const float* zr = z_main + (int64_t)i * C;
+    float l = 0.f, sc = 0.f;
+    if (keep) {
+      l = row_lse(zr, C);
+      sc = gce * (w ? w[yi] : 1.f);
+    }
+    float le = 0.f, dot = 0.f;
+    if (ent) {
+      le = keep ? l : row_lse(zr, C);
+      for (int c = 0; c < C; ++c) {
+        const float p = expf(zr[c] - le);
+        dot += p * ent_slope(p);
+      }
+    }
+    float* d = dz_main + (int64_t)i * C;
+    if (shared) {
+      const float* br = z_other + (int64_t)i * C;
+      const float la = keep ? l : (ent ? le : row_lse(zr, C)), lb = row_lse(br, C);
+      for (int c = 0; c < C; ++c) {
+        const float pk = gkl * (expf(zr[c] - la) - expf(br[c] - lb));
+        float v;
+        if (ce) v = add_parts(keep ? sc * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f)) : 0.f, pk);
+        else v = pk;
+        if (ent) {
+          const float p = expf(zr[c] - le);
+          v = add_parts(v, gent * p * (ent_slope(p) - dot));
+        }
+        d[c] = v;
+      }
+      continue;
+    }
+    for (int c = 0; c < C; ++c) {
+      float v = keep ? sc * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f)) : 0.f;
+      if (ent) {
+        const float p = expf(zr[c] - le);
+        v = add_parts(v, gent * p * (ent_slope(p) - dot));
+      }
+      d[c] = v;
+    }
+    if (dz_xm) {
+      float* dx = dz_xm + (int64_t)i * C;
+      if (kl) {
+        const float* ar = z_xm + (int64_t)i * C;
+        const float* br = z_other + (int64_t)i * C;
+        const float la = row_lse(ar, C), lb = row_lse(br, C);
+        for (int c = 0; c < C; ++c) dx[c] = gkl * (expf(ar[c] - la) - expf(br[c] - lb));
+      } else {
+        for (int c = 0; c < C; ++c) dx[c] = 0.f;
+      }
+    }
+  }
+}
+
+MOPA_API size_t mopa_point_losses_seg_workspace_bytes(int32_t S) {
+  return align_up((size_t)(S > 0 ? S : 1) * PL_SEG_TERMS * PL_MAXGRID * sizeof(double), 256);
+}
+
+// Checks one network's column of the table: its row0 entries are -1 or the running sum of the rows before (the network's rows
+// are the concatenation of its segments), every one given needs the logits, and the sum is the tensor's row count.
+static bool seg_rows_ok(const PointLossSeg* sg, int S, int k, const float* z, int64_t n_rows) {
+  int64_t at = 0;
+  for (int s = 0; s < S; ++s) {
+    if (sg[s].n < 0 || sg[s].n > INT32_MAX) return false;
+    if (sg[s].row0[k] < 0) {
+      if (sg[s].row0[k] != -1) return false;
+      continue;
+    }
+    if (!z || sg[s].row0[k] != at) return false;
+    at += sg[s].n;
+  }
+  return at == (z ? n_rows : 0);
+}
+
+// The loss-and-metric block of all row segments of a merged pass.  z*_main / z*_xm (N2 | N3, C) fp32 contiguous, as in
+// mopa_point_losses_fwd (z*_xm null: that network has no KL term).  segs_host: S <= 8 descriptors of ten int64 each --
+// n, row0_2d, row0_3d (-1: the network takes no part), y_2d, y_3d, acc_mask, conf_2d, conf_3d, acc_out (device pointers,
+// nullable), flags (1 kl, 2 weighted, 4 minent).  Per segment and network: a CE term where labels are given, a KL term with
+// flag 1 where both networks take part, an entropy term with flag 4.  scalars fp32 [S][2][4] = (ce, den, kl, ent); the
+// entries of absent terms are left untouched; a segment of 0 rows gives NaN terms.  status as mopa_point_losses_fwd, shared.
+MOPA_API int mopa_point_losses_seg_fwd(const float* z2_main, const float* z2_xm, const float* z3_main, const float* z3_xm,
+                                       const float* class_weight, const int64_t* segs_host, int32_t S, int64_t N2, int64_t N3,
+                                       int32_t C, int64_t ignore_index, float* scalars, int32_t* status, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  if (S <= 0 || S > PL_MAXSEG || C <= 0 || C > MAXC || !scalars || !segs_host || N2 < 0 || N3 < 0) return MOPA_ERR_ARG;
+  if ((z2_xm && !z2_main) || (z3_xm && !z3_main)) return MOPA_ERR_ARG;
+  const PointLossSeg* sg = reinterpret_cast<const PointLossSeg*>(segs_host);
+  if (!seg_rows_ok(sg, S, 0, z2_main, N2) || !seg_rows_ok(sg, S, 1, z3_main, N3)) return MOPA_ERR_ARG;
+  PointLossSegArgs a;
+  PointLossSegFin f;
+  const float* zx[2] = {z2_xm, z3_xm};
+  int any = 0, grid = 0;
+  size_t lds = 0;
+  for (int s = 0; s < S; ++s) {
+    const PointLossSeg& d = sg[s];
+    const int flags = (int)d.flags;
+    if (d.flags & ~(int64_t)(PL_SEG_KL | PL_SEG_WEIGHTED | PL_SEG_MINENT)) return MOPA_ERR_ARG;
+    if ((flags & PL_SEG_MINENT) && C < 2) return MOPA_ERR_ARG;   // the reference divides by log2(1)
+    int has = 0, mats = 0;
+    for (int k = 0; k < 2; ++k) {
+      const bool in = d.row0[k] >= 0;
+      if (d.y[k] && (!in || !status)) return MOPA_ERR_ARG;
+      if (d.conf[k] && !d.y[k]) return MOPA_ERR_ARG;
+      mats += d.conf[k] ? 1 : 0;
+      if (d.y[k]) has |= 1 << (4 * k);
+      if ((flags & PL_SEG_KL) && d.row0[0] >= 0 && d.row0[1] >= 0 && zx[k]) has |= 2 << (4 * k);
+      if ((flags & PL_SEG_MINENT) && in) has |= 4 << (4 * k);
+    }
+    if (d.acc_mask && (!d.y[1] || !d.acc_out)) return MOPA_ERR_ARG;
+    any |= has;
+    a.seg[s] = d;
+    a.blk0[s] = f.blk0[s] = grid;
+    grid += d.n > 0 ? stream_grid(d.n, LOSS_BLOCK) : 0;   // <= PL_MAXGRID each
+    f.has[s] = has;
+    f.kl_scale[s] = 1.0 / (double)d.n;                    // n = 0: inf, and 0 * inf = NaN as .mean() of nothing
+    f.ent_scale[s] = -1.0 / ((double)d.n * log2((double)C));
+    const size_t need = (size_t)mats * C * C * sizeof(int);   // <= 32 KB at MAXC
+    lds = need > lds ? need : lds;
+  }
+  if (!any) return MOPA_ERR_ARG;
+  if (ws_bytes < mopa_point_losses_seg_workspace_bytes(S)) return MOPA_ERR_WORKSPACE;
+  for (int s = S; s <= PL_MAXSEG; ++s) a.blk0[s] = f.blk0[s] = grid;
+  a.zm[0] = z2_main; a.zm[1] = z3_main; a.zx[0] = z2_xm; a.zx[1] = z3_xm;
+  a.w = class_weight; a.ignore = ignore_index; a.S = S; a.C = C;
+  a.partial = (double*)ws; a.status = status;
+  f.partial = (const double*)ws; f.scalars = scalars;
+  hipStream_t st = (hipStream_t)stream;
+  if (grid) k_point_losses_seg<<<grid, LOSS_BLOCK, lds, st>>>(a);
+  k_point_losses_seg_finalize<<<S, 256, 0, st>>>(f);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// One network's backward over all of its N rows (net 0: the 2D network, 1: the 3D network), the same table.  z_main (N, C) and
+// dz_main are needed; z_xm with dz_xm when the network has KL terms (z_xm == z_main needs dz_xm == dz_main), z_other_main
+// (N_other, C) is the other network's main head, the detached KL target.  scalars: mopa_point_losses_seg_fwd's (the
+// normalisers); g fp32 [S][3]: upstream gradients of (ce, kl, ent) per segment.  Every row of dz_main -- and of dz_xm on a dual
+// head -- is written: zeros where its segment has no term for that head.
+MOPA_API int mopa_point_losses_seg_bwd(int32_t net, const float* z_main, const float* z_xm, const float* z_other_main,
+                                       const float* class_weight, const int64_t* segs_host, int32_t S, int64_t N, int64_t N_other,
+                                       int32_t C, int64_t ignore_index, const float* scalars, const float* g, float* dz_main,
+                                       float* dz_xm, void* stream) {
+  if (net < 0 || net > 1 || S <= 0 || S > PL_MAXSEG || C <= 0 || C > MAXC || !segs_host || N < 0 || N_other < 0) return MOPA_ERR_ARG;
+  if (!z_main || !dz_main || !scalars || !g) return MOPA_ERR_ARG;
+  if ((z_xm != nullptr) != (dz_xm != nullptr) || (z_xm && !z_other_main)) return MOPA_ERR_ARG;
+  if (z_xm && (z_xm == z_main) != (dz_xm == dz_main)) return MOPA_ERR_ARG;
+  const PointLossSeg* sg = reinterpret_cast<const PointLossSeg*>(segs_host);
+  if (!seg_rows_ok(sg, S, net, z_main, N)) return MOPA_ERR_ARG;
+  if (z_other_main && !seg_rows_ok(sg, S, 1 - net, z_other_main, N_other)) return MOPA_ERR_ARG;
+  PointLossSegBwdArgs a;
+  int grid = 0;
+  for (int s = 0; s < S; ++s) {
+    const PointLossSeg& d = sg[s];
+    if (d.flags & ~(int64_t)(PL_SEG_KL | PL_SEG_WEIGHTED | PL_SEG_MINENT)) return MOPA_ERR_ARG;
+    if ((d.flags & PL_SEG_MINENT) && C < 2) return MOPA_ERR_ARG;
+    if (d.y[net] && d.row0[net] < 0) return MOPA_ERR_ARG;
+    a.seg[s] = d;
+    a.blk0[s] = grid;
+    grid += (d.row0[net] >= 0 && d.n > 0) ? stream_grid(d.n, LOSS_BLOCK) : 0;
+  }
+  for (int s = S; s <= PL_MAXSEG; ++s) a.blk0[s] = grid;
+  a.z_main = z_main; a.z_xm = z_xm; a.z_other = z_other_main; a.w = class_weight; a.ignore = ignore_index;
+  a.S = S; a.C = C; a.net = net; a.log2c = log2f((float)C);
+  a.scalars = scalars; a.g = g; a.dz_main = dz_main; a.dz_xm = dz_xm;
+  if (grid) k_point_losses_seg_bwd<<<grid, LOSS_BLOCK, 0, (hipStream_t)stream>>>(a);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
 // ------------------------------------------------------------------------------------------ softmax over the last dim
 __global__ void k_softmax_fwd(const float* __restrict__ z, int64_t N, int C, float* __restrict__ p) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
