@@ -78,7 +78,10 @@ SECTIONS = [
  * refine_pseudo_labels (mopa/data/utils/refine_pseudo_labels.py:5-22) for many (array, scan) segments at once; same bits as
  * mopa_rotate_points_f32 + mopa_voxelize per scan.  Per-scan pointers, sizes and draws are small host arrays (at most 32 scans,
  * 64 segments per call)."""),
-    ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3)."""),
+    ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3).
+ * Not in the reference (opt-in): mopa_grad_stats = per-parameter and total 2-norm, max |g| and non-finite count of the flat gradient
+ * (what torch.nn.utils.clip_grad_norm_ and torch.isfinite would compute, without a host read), mopa_adam_flat_guarded = the same
+ * update clipped or skipped by the step record that pass leaves in device memory."""),
 ]
 
 HEAD = """/* libmopa_hip.so -- C ABI of the MI355X-native MoPA hot path (gfx950 only).

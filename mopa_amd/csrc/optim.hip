@@ -3,35 +3,210 @@
 // (the reference's optimiser: mopa/common/solver/build.py:7-21 -> getattr(torch.optim, 'Adam'), yaml lr 1e-3):
 //   g += wd * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
 //   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+//
+// Gradient statistics and the guarded update (opt-in; FlatAdam(max_grad_norm=, skip_nonfinite=)): mopa_grad_stats reads the flat
+// gradient once and leaves, in device memory, the norm / max |g| / non-finite count of every parameter and a 32-byte step record
+// (total norm, clip coefficient of torch.nn.utils.clip_grad_norm_, go / no-go); mopa_adam_flat_guarded is k_adam_flat's body behind
+// that record.  No host read anywhere, no atomics: slab records summed in a fixed order (same bits run to run, whatever the grid).
 #include "common.h"
 
-__global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
-                                                    float wd, float bc1, float bc2_sqrt, float grad_scale) {
+// The update of both Adam kernels: ONE body, so that the guarded kernel with coef == 1 leaves the plain kernel's bits.  Which
+// products fuse into an FMA is WRITTEN OUT (contraction is off in this function): left to the compiler it follows the code around
+// the expression -- the same source inlined into a second kernel fused other operands than k_adam_flat did on its own (the same
+// instruction counts, other bits; DESIGN 3.3 item 8 saw it across translation units).  The choices below are the ones every
+// build of k_adam_flat so far has made, float4 loop and scalar tail each as it was, so no trained weight moves by a bit.
+__device__ __forceinline__ void adam_flat_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                               float wd, float bc1, float bc2_sqrt, float grad_scale, int64_t first,
+                                               int64_t stride) {
+#pragma clang fp contract(off)
   const int64_t n4 = n >> 2;
   const float step = lr / bc1;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = first; i < n4; i += stride) {
     float4 pv = reinterpret_cast<float4*>(p)[i];
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
     float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
     float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float gg = gp[k] * grad_scale + wd * pp[k];
-      mp[k] = b1 * mp[k] + (1.f - b1) * gg;
-      vp[k] = b2 * vp[k] + (1.f - b2) * gg * gg;
+      const float gg = __builtin_fmaf(gp[k], grad_scale, wd * pp[k]);
+      mp[k] = __builtin_fmaf(b1, mp[k], (1.f - b1) * gg);
+      vp[k] = __builtin_fmaf(b2, vp[k], (1.f - b2) * gg * gg);
       pp[k] -= step * mp[k] / (sqrtf(vp[k]) / bc2_sqrt + eps);
     }
     reinterpret_cast<float4*>(p)[i] = pv;
     reinterpret_cast<float4*>(m)[i] = mv;
     reinterpret_cast<float4*>(v)[i] = vv;
   }
-  for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gg = g[i] * grad_scale + wd * p[i];
+  for (int64_t i = (n4 << 2) + first; i < n; i += stride) {   // (only the first sum was ever fused here)
+    const float gg = __builtin_fmaf(g[i], grad_scale, wd * p[i]);
     m[i] = b1 * m[i] + (1.f - b1) * gg;
     v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
     p[i] -= step * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
   }
+}
+
+__global__ __launch_bounds__(256) void k_adam_flat(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                                    float wd, float bc1, float bc2_sqrt, float grad_scale) {
+  adam_flat_body(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                 (int64_t)gridDim.x * blockDim.x);
+}
+
+// ---- gradient statistics
+#define GS_CHUNK 8192          // floats per chunk: 256 threads x 8 float4 (23.6 M floats of the 2D network = ~2,900 chunks)
+#define GS_LOADS (GS_CHUNK / 4 / 256)
+
+struct GsChunk {               // one record of the DEVICE chunk table: grads[lo, hi) belongs to parameter `param`
+  int64_t param, lo, hi;       // lo % 4 == 0, 0 <= hi - lo <= GS_CHUNK; records sorted by param (FlatAdam: optim.py::stat_chunks)
+};
+struct GsSlab {                // what the partial pass leaves per chunk (16 bytes)
+  double sumsq;                // sum of g^2 in double (a float product is exact there); NaN / Inf elements go in as they are
+  float absmax;                // max |g| over the finite elements
+  int nonfinite;               // NaN and +-Inf elements
+};
+struct GsStepRec {             // the step record (32 bytes) -- read by k_adam_flat_guarded, kept across steps for the counters
+  float norm;                  // |grad_scale| * sqrt(sum over the whole buffer)
+  int nonfinite;
+  float coef;                  // clip_grad_norm_'s factor: max_norm / (norm + 1e-6f) clamped to 1; 1 without clipping
+  int applied;                 // !(skip_nonfinite && nonfinite > 0)
+  int64_t n_skipped, n_clipped;
+};
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// One block per chunk at a time (grid-stride).  The order of the additions is a function of the chunk alone: thread t adds its
+// float4s in index order (t, t + 256, ...) and then tail element t, wave_sum_d's butterfly, the four waves in wave order.
+__global__ __launch_bounds__(256) void k_grad_stats_partial(const float* __restrict__ g, const GsChunk* __restrict__ tab, int n_chunks,
+                                                             GsSlab* __restrict__ slab) {
+  __shared__ double s_sum[4];
+  __shared__ float s_max[4];
+  __shared__ int s_nf[4];
+  const int tid = threadIdx.x;
+  for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+    const int64_t lo = tab[c].lo;
+    int64_t len64 = tab[c].hi - lo;
+    if (len64 < 0 || lo < 0 || (lo & 3)) len64 = 0;   // a record this kernel cannot read as float4s counts as empty
+    const int len = (int)(len64 > GS_CHUNK ? GS_CHUNK : len64), n4 = len >> 2;
+    const float4* g4 = reinterpret_cast<const float4*>(g + lo);
+    float4 x[GS_LOADS];
+#pragma unroll
+    for (int k = 0; k < GS_LOADS; ++k) {              // every load in flight before the first add; +0 for the absent ones is exact
+      const int i = tid + k * 256;
+      x[k] = i < n4 ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float tail = tid < (len & 3) ? g[lo + (n4 << 2) + tid] : 0.f;
+    double sum = 0.0;
+    float amax = 0.f;
+    int nf = 0;
+    auto take = [&](float e) {
+      const bool fin = (__float_as_uint(e) & 0x7f800000u) != 0x7f800000u;
+      sum += (double)e * (double)e;
+      amax = fmaxf(amax, fin ? fabsf(e) : 0.f);
+      nf += fin ? 0 : 1;
+    };
+#pragma unroll
+    for (int k = 0; k < GS_LOADS; ++k) { take(x[k].x); take(x[k].y); take(x[k].z); take(x[k].w); }
+    take(tail);
+    sum = wave_sum_d(sum);
+    amax = wave_max(amax);
+    nf = wave_sum_i(nf);
+    if ((tid & 63) == 0) { s_sum[tid >> 6] = sum; s_max[tid >> 6] = amax; s_nf[tid >> 6] = nf; }
+    __syncthreads();
+    if (tid == 0) {
+      GsSlab r;
+      r.sumsq = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
+      r.absmax = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+      r.nonfinite = s_nf[0] + s_nf[1] + s_nf[2] + s_nf[3];
+      slab[c] = r;
+    }
+    __syncthreads();
+  }
+}
+
+// One block.  Thread t of a round owns parameter base + t: it finds the parameter's records in the sorted table (two binary
+// searches, stepped together) and adds their slabs in chunk order; thread 0 then adds the round's 256 sums in parameter order into
+// the running total.  Any number of parameters: nothing here is sized by it.
+__global__ __launch_bounds__(256) void k_grad_stats_final(const GsSlab* __restrict__ slab, const GsChunk* __restrict__ tab, int n_chunks,
+                                                           int n_params, float gs_abs, float max_norm, int skip_nonfinite,
+                                                           float* __restrict__ stats, GsStepRec* __restrict__ rec) {
+  __shared__ double s_sum[256];
+  __shared__ int s_nf[256];
+  const int tid = threadIdx.x;
+  float* norm = stats;
+  float* absmax = stats + n_params;
+  int* nonfinite = reinterpret_cast<int*>(stats + 2 * (int64_t)n_params);
+  double total = 0.0;          // thread 0's
+  int64_t total_nf = 0;
+  for (int base = 0; base < n_params; base += 256) {
+    const int p = base + tid;
+    double sum = 0.0;
+    float amax = 0.f;
+    int nf = 0;
+    if (p < n_params) {
+      int a0 = 0, b0 = n_chunks, a1 = 0, b1 = n_chunks;   // first record with param >= p, and with param >= p + 1
+      while (a0 < b0 || a1 < b1) {
+        if (a0 < b0) { const int mid = (a0 + b0) >> 1; if (tab[mid].param < p) a0 = mid + 1; else b0 = mid; }
+        if (a1 < b1) { const int mid = (a1 + b1) >> 1; if (tab[mid].param <= p) a1 = mid + 1; else b1 = mid; }
+      }
+      for (int c = a0; c < a1; c += 16) {                 // 16 records in flight per round trip; an absent one adds +0: exact
+        GsSlab r[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) r[k] = c + k < a1 ? slab[c + k] : GsSlab{0.0, 0.f, 0};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          sum += r[k].sumsq;
+          amax = fmaxf(amax, r[k].absmax);
+          nf += r[k].nonfinite;
+        }
+      }
+      norm[p] = (float)(sqrt(sum) * (double)gs_abs);
+      absmax[p] = (float)((double)amax * (double)gs_abs);
+      nonfinite[p] = nf;
+    }
+    s_sum[tid] = sum;
+    s_nf[tid] = nf;
+    __syncthreads();
+    if (tid == 0) {                                       // (threads past n_params left zeros)
+      for (int j = 0; j < 256 && base + j < n_params; j += 32) {
+#pragma unroll
+        for (int k = 0; k < 32; ++k) { total += s_sum[j + k]; total_nf += s_nf[j + k]; }
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const float tnorm = (float)(sqrt(total) * (double)gs_abs);
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+      const float c = max_norm / (tnorm + 1e-6f);
+      coef = c >= 1.f ? 1.f : c;                        // a NaN norm leaves a NaN coefficient, as torch's clamp does
+    }
+    const int applied = !(skip_nonfinite && total_nf > 0);
+    rec->norm = tnorm;
+    rec->nonfinite = (int)(total_nf > 0x7fffffff ? 0x7fffffff : total_nf);
+    rec->coef = coef;
+    rec->applied = applied;
+    if (!applied) rec->n_skipped += 1;
+    else if (coef < 1.f) rec->n_clipped += 1;
+  }
+}
+
+// k_adam_flat behind the step record: nothing is stored when the step is not applied, else the gradient is scaled by
+// grad_scale * coef -- one multiply, formed once, so coef == 1 is k_adam_flat bit for bit.
+__global__ __launch_bounds__(256) void k_adam_flat_guarded(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                                            float wd, float bc1, float bc2_sqrt, float grad_scale,
+                                                            const GsStepRec* __restrict__ rec) {
+  const int applied = rec->applied;
+  const float coef = rec->coef;
+  if (!applied) return;
+  adam_flat_body(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale * coef, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                 (int64_t)gridDim.x * blockDim.x);
 }
 
 // bias_correction1 = 1 - beta1^t, bias_correction2_sqrt = sqrt(1 - beta2^t) are computed by the caller (host scalars).
@@ -44,6 +219,55 @@ MOPA_API int mopa_adam_flat(float* params, const float* grads, float* exp_avg, f
   k_adam_flat<<<stream_grid(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
                                                                             eps, weight_decay, bias_correction1,
                                                                             bias_correction2_sqrt, grad_scale);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// Floats per chunk of mopa_grad_stats' chunk table (a compile-time constant, a multiple of 4).
+MOPA_API int mopa_grad_stats_chunk(void) { return GS_CHUNK; }
+
+// One slab record per chunk.
+MOPA_API size_t mopa_grad_stats_workspace_bytes(int64_t n_chunks) { return sizeof(GsSlab) * (size_t)(n_chunks > 0 ? n_chunks : 1); }
+
+// Statistics of grad_scale * grads, per parameter and over the whole buffer, in two launches.
+//   chunk_tab  DEVICE table of n_chunks records {int64 param, lo, hi}: grads[lo, hi) is a piece of parameter `param`;
+//              lo % 4 == 0, hi - lo <= mopa_grad_stats_chunk(), records sorted by param, every element in exactly one record
+//   stats      float norm[n_params], float absmax[n_params], int32 nonfinite[n_params]  (3 * n_params * 4 bytes):
+//              norm = (float)(sqrt(sum g^2) * |grad_scale|) formed in double, absmax over the finite elements, scaled alike
+//   rec        32 bytes, 8-byte aligned: float norm (NaN / Inf elements propagate), int32 nonfinite, float coef, int32 applied,
+//              int64 n_skipped, int64 n_clipped.  coef = max_norm / (norm + 1e-6f) in float, exactly 1 where that is >= 1 or
+//              max_norm <= 0; applied = !(skip_nonfinite && nonfinite > 0).  The two counters are ADDED to (zero them once):
+//              n_skipped when applied == 0, n_clipped when applied and coef < 1.
+//   ws         mopa_grad_stats_workspace_bytes(n_chunks), 16-byte aligned
+MOPA_API int mopa_grad_stats(const float* grads, const void* chunk_tab, int64_t n_chunks, int64_t n_params, float grad_scale,
+                             float max_norm, int skip_nonfinite, float* stats, void* rec, void* ws, size_t ws_bytes, void* stream) {
+  if (n_chunks <= 0 || n_params <= 0 || n_chunks > INT32_MAX || n_params > INT32_MAX / 4) return MOPA_ERR_ARG;
+  if (!grads || !chunk_tab || !stats || !rec || !ws) return MOPA_ERR_ARG;
+  if (((uintptr_t)grads & 15) != 0 || ((uintptr_t)ws & 15) != 0 || ((uintptr_t)chunk_tab & 7) != 0 || ((uintptr_t)rec & 7) != 0 ||
+      ((uintptr_t)stats & 3) != 0)
+    return MOPA_ERR_ARG;
+  if (ws_bytes < mopa_grad_stats_workspace_bytes(n_chunks)) return MOPA_ERR_WORKSPACE;
+  const int grid = (int)(n_chunks < 2048 ? n_chunks : 2048);
+  k_grad_stats_partial<<<grid, 256, 0, (hipStream_t)stream>>>(grads, (const GsChunk*)chunk_tab, (int)n_chunks, (GsSlab*)ws);
+  MOPA_CHECK_LAUNCH();
+  k_grad_stats_final<<<1, 256, 0, (hipStream_t)stream>>>((const GsSlab*)ws, (const GsChunk*)chunk_tab, (int)n_chunks, (int)n_params,
+                                                         fabsf(grad_scale), max_norm, skip_nonfinite, stats, (GsStepRec*)rec);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// mopa_adam_flat behind the step record `rec` of mopa_grad_stats (device memory, read by every thread once): no store at all
+// when rec.applied == 0, else the same update with grad_scale * rec.coef in place of grad_scale.
+MOPA_API int mopa_adam_flat_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, float bias_correction1,
+                                    float bias_correction2_sqrt, float grad_scale, const void* rec, void* stream) {
+  if (n <= 0 || !rec) return MOPA_ERR_ARG;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) return MOPA_ERR_ARG;
+  if (((uintptr_t)rec & 7) != 0) return MOPA_ERR_ARG;
+  k_adam_flat_guarded<<<stream_grid(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, lr, beta1,
+                                                                                    beta2, eps, weight_decay, bias_correction1,
+                                                                                    bias_correction2_sqrt, grad_scale,
+                                                                                    (const GsStepRec*)rec);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }

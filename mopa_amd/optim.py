@@ -20,7 +20,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from ._lib import GRAD_DONE_HOOKS, WEIGHTS_EPOCH, call, ptr, stream
+from ._lib import GRAD_DONE_HOOKS, WEIGHTS_EPOCH, call, ptr, query, stream, workspace
 
 # MOPA_FORCE_COLLECTIVES=1: issue the all-reduce in a one-rank process group too (exercises the RCCL path on a 1-GPU box)
 _FORCE_COLLECTIVES = os.environ.get("MOPA_FORCE_COLLECTIVES") == "1"
@@ -37,12 +37,82 @@ class _Works:
             w.wait()
 
 
+def stat_chunks(slices, chunk):
+    """The chunk table of ``mopa_grad_stats`` for ``FlatAdam._slices`` (``(offset, numel)`` per parameter): a list of
+    ``(parameter index, lo, hi)`` ranges of the flat buffer, in parameter order.  Every parameter element is in exactly one
+    chunk, no chunk crosses a parameter or touches the padding behind one, ``hi - lo <= chunk`` and ``lo % 4 == 0`` (the kernel
+    reads a chunk as float4s from ``lo``)."""
+    chunk = int(chunk)
+    if chunk <= 0 or chunk % 4:
+        raise ValueError("stat_chunks: the chunk length must be a positive multiple of 4")
+    out = []
+    for i, (off, n) in enumerate(slices):
+        if off % 4:
+            raise ValueError("stat_chunks: parameter %d starts at %d, not at a multiple of 4" % (i, off))
+        out += [(i, lo, min(lo + chunk, off + n)) for lo in range(off, off + n, chunk)]
+    return out
+
+
+class GradStats:
+    """What ``mopa_grad_stats`` left on the device for one gradient buffer -- tensors, no host read.  All norms are of
+    ``grad_scale * g``.  The tensors are views of buffers the optimizer reuses: the next ``step()`` (for ``last_stats``) or
+    ``grad_stats()`` call overwrites them (and returns this same object), so ``clone()`` what has to outlive it.
+
+    ``norm`` () float32, ``nonfinite`` () int32: the whole buffer (a NaN / Inf element makes ``norm`` NaN / Inf, as torch's
+    norm of norms does); ``param_norm`` / ``param_absmax`` (P,) float32 and ``param_nonfinite`` (P,) int32: per parameter, in
+    the optimizer's parameter order (``param_absmax`` is over the finite elements).  After a guarded ``step()`` also ``coef`` ()
+    float32 (the clip factor applied, 1 = not clipped), ``applied`` () int32 (0 = the step was skipped) and the running
+    counters ``n_skipped`` / ``n_clipped`` () int64; ``None`` otherwise."""
+
+    def __init__(self, norm, nonfinite, param_norm, param_absmax, param_nonfinite, coef=None, applied=None, n_skipped=None,
+                 n_clipped=None):
+        self.norm, self.nonfinite = norm, nonfinite
+        self.param_norm, self.param_absmax, self.param_nonfinite = param_norm, param_absmax, param_nonfinite
+        self.coef, self.applied, self.n_skipped, self.n_clipped = coef, applied, n_skipped, n_clipped
+
+    def summary(self, names=None, top=5):
+        """One line for the log.  The ONLY method here that reads back from the device (it synchronises): call it at the logging
+        period, not every step.  Names the ``top`` parameters by norm and every parameter with non-finite entries; ``names``:
+        one name per parameter (``[n for n, p in model.named_parameters() if p.requires_grad]``), default their indices."""
+        pn, pnf = self.param_norm.detach().cpu(), self.param_nonfinite.detach().cpu()
+        name = (lambda i: str(names[i])) if names is not None else (lambda i: "#%d" % i)
+        parts = ["grad norm %.4g" % float(self.norm), "non-finite %d" % int(self.nonfinite)]
+        if self.applied is not None:
+            parts.append("coef %.4g, %s, skipped %d, clipped %d so far" % (float(self.coef), "applied" if int(self.applied) else "SKIPPED",
+                                                                          int(self.n_skipped), int(self.n_clipped)))
+        order = sorted(range(len(pn)), key=lambda i: -float(pn[i].nan_to_num(nan=float("inf"))))[:max(0, int(top))]
+        if order:
+            parts.append("largest: " + ", ".join("%s %.4g" % (name(i), float(pn[i])) for i in order))
+        bad = [i for i in range(len(pnf)) if int(pnf[i]) > 0]
+        if bad:
+            parts.append("non-finite in: " + ", ".join("%s (%d)" % (name(i), int(pnf[i])) for i in bad))
+        return "; ".join(parts)
+
+
 class FlatAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, checkpoint_shapes=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, checkpoint_shapes=None,
+                 max_grad_norm=None, skip_nonfinite=False):
         """``checkpoint_shapes``: optional list (one entry per parameter, ``None`` = the parameter's own shape) of the shapes
         the moment tensors take in ``state_dict()`` -- ``mopa_amd.models.scn_unet.checkpoint_shapes(model)`` gives
         SparseConvNet's 4-D conv-weight layout so that a reference-side ``torch.optim.Adam.load_state_dict`` of our
-        checkpoint pairs every moment with a parameter of the same shape."""
+        checkpoint pairs every moment with a parameter of the same shape.
+
+        ``max_grad_norm`` / ``skip_nonfinite`` (the guard; both off by default, and then ``step()`` is the single
+        ``mopa_adam_flat`` launch it always was): with either set, ``step()`` first measures the gradient on the device
+        (``mopa_grad_stats``: one read of the flat gradient, per-parameter and total 2-norm of ``grad_scale * g``, max |g|,
+        non-finite count) and then runs ``mopa_adam_flat_guarded``, which takes its decisions from device memory -- no host
+        read, no sync.  ``max_grad_norm``: the update uses ``coef * grad_scale * g`` with ``coef = max_grad_norm / (norm + 1e-6)``
+        clamped to 1, ``torch.nn.utils.clip_grad_norm_``'s formula in float32 (norm type 2).  ``skip_nonfinite``: a step whose
+        gradient holds a NaN or Inf writes nothing -- ``flat``, ``exp_avg`` and ``exp_avg_sq`` keep their bits.  ``last_stats``
+        holds the ``GradStats`` of the last guarded step.  Both are attributes of the optimizer, not ``param_groups`` entries:
+        ``state_dict()`` keeps ``torch.optim.Adam``'s layout.  Differences from torch, on purpose:
+          * ``p.grad`` is never modified (``clip_grad_norm_`` rewrites the gradients; here the factor goes into the update);
+          * the step count ``t`` (bias corrections are host scalars) advances on a skipped step too -- torch's fused Adam with
+            ``found_inf`` rolls its device-side step back.  In exchange a guarded optimizer in which nothing triggers is
+            bit-identical to the plain one, at the price of a bias correction a few steps ahead after a skip early in training;
+          * there is no ``error_if_nonfinite`` (it needs a host sync): read ``last_stats.nonfinite`` at the logging period.
+        Data parallel: ``step()`` runs after ``all_reduce()`` has been waited for, so every rank measures the same summed buffer
+        -- a sum all-reduce leaves identical bits on all ranks -- and takes the same decision; no further collective."""
         params = [p for p in params if p.requires_grad]
         if not params:
             raise ValueError("FlatAdam got no parameters")
@@ -73,6 +143,12 @@ class FlatAdam(torch.optim.Optimizer):
         self._ckpt_shapes = list(checkpoint_shapes) if checkpoint_shapes is not None else [None] * len(params)
         if len(self._ckpt_shapes) != len(params):
             raise ValueError("checkpoint_shapes must have one entry per trainable parameter")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("FlatAdam: max_grad_norm must be positive (None = no clipping)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.last_stats = None        # GradStats of the last guarded step()
+        self._gs = None               # device side of mopa_grad_stats: built on first use
 
     # ---- reference-facing conveniences (kept from round 1)
     @property
@@ -247,6 +323,39 @@ class FlatAdam(torch.optim.Optimizer):
         with torch.cuda.stream(self._comm):
             self._bucket_works.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, async_op=True))
 
+    # ---- gradient statistics and the guarded step (csrc/optim.hip)
+    def _grad_stats(self, grad_scale, max_norm, skip_nonfinite, which):
+        if self.flat.device.type != "cuda":
+            raise RuntimeError("FlatAdam gradient statistics need the HIP extension on an MI355X (no CPU fallback)")
+        if self._gs is None:    # once: the chunk table goes up; a (stats, step record) pair and its views for step(), one for grad_stats()
+            dev, n_par = self.grad.device, len(self.params)
+            tab = torch.tensor(stat_chunks(self._slices, query("mopa_grad_stats_chunk")), dtype=torch.int64).reshape(-1, 3)
+            self._gs = {"tab": tab.to(dev), "n_chunks": int(tab.shape[0]),
+                        "ws_bytes": query("mopa_grad_stats_workspace_bytes", int(tab.shape[0]))}
+            for which_ in ("step", "query"):
+                stats = torch.zeros(3, n_par, dtype=torch.float32, device=dev)
+                rec = torch.zeros(8, dtype=torch.int32, device=dev)   # csrc/optim.hip::GsStepRec; the counters start at 0
+                out = GradStats(rec[0:1].view(torch.float32)[0], rec[1], stats[0], stats[1], stats[2].view(torch.int32))
+                if which_ == "step":
+                    counters = rec[4:8].view(torch.int64)
+                    out.coef, out.applied, out.n_skipped, out.n_clipped = rec[2:3].view(torch.float32)[0], rec[3], counters[0], counters[1]
+                self._gs[which_] = (stats, rec, out)
+        gs = self._gs
+        stats, rec, out = gs[which]
+        ws = workspace.get(gs["ws_bytes"], self.grad.device)
+        call("mopa_grad_stats", ptr(self.grad), ptr(gs["tab"]), gs["n_chunks"], len(self.params), grad_scale, max_norm,
+             int(skip_nonfinite), ptr(stats), ptr(rec), ptr(ws), gs["ws_bytes"], stream())
+        return out, rec
+
+    @torch.no_grad()
+    def grad_stats(self, grad_scale: float = 1.0) -> GradStats:
+        """Measure the flat gradient as it stands (after backward / ``all_reduce()``), with or without the guard: enqueues
+        ``mopa_grad_stats`` on the current stream and returns device tensors -- no sync.  Touches neither ``last_stats`` nor the
+        guard's counters."""
+        if not getattr(self, "_checked", False):
+            self._check_grads()
+        return self._grad_stats(grad_scale, 0.0, False, "query")[0]
+
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0, closure=None):
         """``step()`` / ``step(grad_scale)`` / ``step(closure)``: torch's convention puts the closure first, so a callable in
@@ -266,11 +375,17 @@ class FlatAdam(torch.optim.Optimizer):
             raise RuntimeError("FlatAdam.step needs the HIP extension on an MI355X (no CPU fallback)")
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        self.t += 1
-        call("mopa_adam_flat", ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
-             float(g["lr"]), b1, b2, g["eps"], g["weight_decay"], 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t),
-             grad_scale, stream())
-        WEIGHTS_EPOCH[0] += 1   # cached weight re-layouts (dense2d / sparse3d) are stale now
+        self.t += 1             # on a skipped step too (the bias corrections are host scalars): see __init__
+        if self.max_grad_norm is None and not self.skip_nonfinite:
+            call("mopa_adam_flat", ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
+                 float(g["lr"]), b1, b2, g["eps"], g["weight_decay"], 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t),
+                 grad_scale, stream())
+        else:
+            self.last_stats, rec = self._grad_stats(grad_scale, self.max_grad_norm or 0.0, self.skip_nonfinite, "step")
+            call("mopa_adam_flat_guarded", ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
+                 float(g["lr"]), b1, b2, g["eps"], g["weight_decay"], 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t),
+                 grad_scale, ptr(rec), stream())
+        WEIGHTS_EPOCH[0] += 1   # cached weight re-layouts (dense2d / sparse3d) are stale now (a skipped step rebuilds them unchanged)
         return loss
 
     # ---- checkpointing in torch.optim.Adam's layout (mopa/common/utils/checkpoint.py:48-49,76-77)
