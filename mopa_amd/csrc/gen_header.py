@@ -81,7 +81,9 @@ SECTIONS = [
     ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3).
  * Not in the reference (opt-in): mopa_grad_stats = per-parameter and total 2-norm, max |g| and non-finite count of the flat gradient
  * (what torch.nn.utils.clip_grad_norm_ and torch.isfinite would compute, without a host read), mopa_adam_flat_guarded = the same
- * update clipped or skipped by the step record that pass leaves in device memory."""),
+ * update clipped or skipped by the step record that pass leaves in device memory.
+ * The other optimizers that call builds by name (getattr(torch.optim, TYPE); mopa/common/config/base.py:42-70 names SGD with
+ * momentum / dampening): mopa_sgd_flat == torch.optim.SGD, mopa_adamw_flat == torch.optim.AdamW, each with its guarded form."""),
 ]
 
 HEAD = """/* libmopa_hip.so -- C ABI of the MI355X-native MoPA hot path (gfx950 only).

@@ -8,6 +8,10 @@
 // gradient once and leaves, in device memory, the norm / max |g| / non-finite count of every parameter and a 32-byte step record
 // (total norm, clip coefficient of torch.nn.utils.clip_grad_norm_, go / no-go); mopa_adam_flat_guarded is k_adam_flat's body behind
 // that record.  No host read anywhere, no atomics: slab records summed in a fixed order (same bits run to run, whatever the grid).
+//
+// The same for the other optimizers the reference's config can name (FlatSGD, FlatAdamW): mopa_sgd_flat == torch.optim.SGD
+// (momentum, dampening, Nesterov, L2 weight decay), mopa_adamw_flat == torch.optim.AdamW (decoupled weight decay), each with a
+// guarded form behind the same step record.
 #include "common.h"
 
 // The update of both Adam kernels: ONE body, so that the guarded kernel with coef == 1 leaves the plain kernel's bits.  Which
@@ -209,6 +213,126 @@ __global__ __launch_bounds__(256) void k_adam_flat_guarded(float* __restrict__ p
                  (int64_t)gridDim.x * blockDim.x);
 }
 
+// ---- AdamW (torch.optim.AdamW): decoupled weight decay, p *= 1 - lr * wd, then Adam's update with no L2 term in the gradient.
+// A body of its own, so that adam_flat_body -- and with it every bit mopa_adam_flat has ever left -- stays as it is; the pairings
+// are written out for the same reason, the same ones in the float4 loop and in the tail.
+__device__ __forceinline__ float adamw_one(float p, float g, float& m, float& v, float decay, float step, float b1, float b2, float eps,
+                                           float bc2_sqrt, float grad_scale) {
+#pragma clang fp contract(off)
+  const float gg = g * grad_scale;
+  p = p * decay;
+  m = __builtin_fmaf(b1, m, (1.f - b1) * gg);
+  v = __builtin_fmaf(b2, v, (1.f - b2) * gg * gg);
+  return p - step * m / (sqrtf(v) / bc2_sqrt + eps);
+}
+
+__device__ __forceinline__ void adamw_flat_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                                float wd, float bc1, float bc2_sqrt, float grad_scale, int64_t first,
+                                                int64_t stride) {
+#pragma clang fp contract(off)
+  const int64_t n4 = n >> 2;
+  const float step = lr / bc1;
+  const float decay = 1.f - lr * wd;
+  for (int64_t i = first; i < n4; i += stride) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+    float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pp[k] = adamw_one(pp[k], gp[k], mp[k], vp[k], decay, step, b1, b2, eps, bc2_sqrt, grad_scale);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  for (int64_t i = (n4 << 2) + first; i < n; i += stride)
+    p[i] = adamw_one(p[i], g[i], m[i], v[i], decay, step, b1, b2, eps, bc2_sqrt, grad_scale);
+}
+
+__global__ __launch_bounds__(256) void k_adamw_flat(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                                     float wd, float bc1, float bc2_sqrt, float grad_scale) {
+  adamw_flat_body(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                  (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void k_adamw_flat_guarded(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
+                                                             float wd, float bc1, float bc2_sqrt, float grad_scale,
+                                                             const GsStepRec* __restrict__ rec) {
+  const int applied = rec->applied;
+  const float coef = rec->coef;
+  if (!applied) return;           // (the decay is part of the step: a skipped step leaves p alone too)
+  adamw_flat_body(p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, grad_scale * coef, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                  (int64_t)gridDim.x * blockDim.x);
+}
+
+// ---- SGD (torch.optim.SGD, element for element):
+//   g' = grad_scale g + wd p;  buf = g' on the first applied step, else momentum buf + (1 - dampening) g';
+//   u = g' + momentum buf (nesterov) | buf | g' (momentum == 0);  p -= lr u
+// `buf` is not touched (and may be null) when momentum == 0.  One body for the plain and the guarded kernel, pairings written out.
+__device__ __forceinline__ float sgd_one(float p, float g, float& b, float lr, float mom, float undamp, float wd, bool use_mom,
+                                         bool nesterov, bool first, float grad_scale) {
+#pragma clang fp contract(off)
+  const float gg = __builtin_fmaf(g, grad_scale, wd * p);
+  float u = gg;
+  if (use_mom) {
+    b = first ? gg : __builtin_fmaf(mom, b, undamp * gg);
+    u = nesterov ? __builtin_fmaf(mom, b, gg) : b;
+  }
+  return __builtin_fmaf(-lr, u, p);
+}
+
+__device__ __forceinline__ void sgd_flat_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
+                                              float lr, float mom, float damp, float wd, bool nesterov, bool first, float grad_scale,
+                                              int64_t first_i, int64_t stride) {
+#pragma clang fp contract(off)
+  const int64_t n4 = n >> 2;
+  const bool use_mom = mom != 0.f;
+  const float undamp = 1.f - damp;
+  for (int64_t i = first_i; i < n4; i += stride) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (use_mom && !first) bv = reinterpret_cast<float4*>(buf)[i];
+    float* pp = &pv.x; const float* gp = &gv.x; float* bp = &bv.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pp[k] = sgd_one(pp[k], gp[k], bp[k], lr, mom, undamp, wd, use_mom, nesterov, first, grad_scale);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    if (use_mom) reinterpret_cast<float4*>(buf)[i] = bv;
+  }
+  for (int64_t i = (n4 << 2) + first_i; i < n; i += stride) {
+    float b = (use_mom && !first) ? buf[i] : 0.f;
+    p[i] = sgd_one(p[i], g[i], b, lr, mom, undamp, wd, use_mom, nesterov, first, grad_scale);
+    if (use_mom) buf[i] = b;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_sgd_flat(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
+                                                   float lr, float mom, float damp, float wd, int nesterov, int first, float grad_scale) {
+  sgd_flat_body(p, g, buf, n, lr, mom, damp, wd, nesterov != 0, first != 0, grad_scale, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                (int64_t)gridDim.x * blockDim.x);
+}
+
+// k_sgd_flat behind the step record.  "First" is not the host's to know here (whether step 1 was applied is decided on the device):
+// it is read from `buf_valid`, one int32 in device memory that is 0 until a step has been applied.  k_sgd_mark_valid, enqueued
+// behind this kernel on the same stream, sets it -- after every thread here has read it.
+__global__ __launch_bounds__(256) void k_sgd_flat_guarded(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                           int64_t n, float lr, float mom, float damp, float wd, int nesterov,
+                                                           const int* __restrict__ buf_valid, float grad_scale,
+                                                           const GsStepRec* __restrict__ rec) {
+  const int applied = rec->applied;
+  const float coef = rec->coef;
+  if (!applied) return;
+  const bool first = buf_valid != nullptr && *buf_valid == 0;
+  sgd_flat_body(p, g, buf, n, lr, mom, damp, wd, nesterov != 0, first, grad_scale * coef, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                (int64_t)gridDim.x * blockDim.x);
+}
+
+__global__ void k_sgd_mark_valid(int* __restrict__ buf_valid, const GsStepRec* __restrict__ rec) {
+  if (blockIdx.x == 0 && threadIdx.x == 0 && rec->applied) *buf_valid = 1;
+}
+
 // bias_correction1 = 1 - beta1^t, bias_correction2_sqrt = sqrt(1 - beta2^t) are computed by the caller (host scalars).
 // grad_scale multiplies the gradient first (1/world_size after a sum all-reduce).
 MOPA_API int mopa_adam_flat(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -269,5 +393,72 @@ MOPA_API int mopa_adam_flat_guarded(float* params, const float* grads, float* ex
                                                                                     bias_correction2_sqrt, grad_scale,
                                                                                     (const GsStepRec*)rec);
   MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// torch.optim.AdamW on the flat buffer: mopa_adam_flat's arguments; weight_decay multiplies the parameter (p *= 1 - lr * wd) and
+// stays out of the gradient.
+MOPA_API int mopa_adamw_flat(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                             float beta1, float beta2, float eps, float weight_decay, float bias_correction1,
+                             float bias_correction2_sqrt, float grad_scale, void* stream) {
+  if (n <= 0) return MOPA_ERR_ARG;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) return MOPA_ERR_ARG;
+  k_adamw_flat<<<stream_grid(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2,
+                                                                             eps, weight_decay, bias_correction1,
+                                                                             bias_correction2_sqrt, grad_scale);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// mopa_adamw_flat behind the step record of mopa_grad_stats, as mopa_adam_flat_guarded is mopa_adam_flat behind it.
+MOPA_API int mopa_adamw_flat_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, float bias_correction1,
+                                     float bias_correction2_sqrt, float grad_scale, const void* rec, void* stream) {
+  if (n <= 0 || !rec) return MOPA_ERR_ARG;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) return MOPA_ERR_ARG;
+  if (((uintptr_t)rec & 7) != 0) return MOPA_ERR_ARG;
+  k_adamw_flat_guarded<<<stream_grid(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(params, grads, exp_avg, exp_avg_sq, n, lr, beta1,
+                                                                                     beta2, eps, weight_decay, bias_correction1,
+                                                                                     bias_correction2_sqrt, grad_scale,
+                                                                                     (const GsStepRec*)rec);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// torch.optim.SGD on the flat buffer.  first != 0: this is the first step that writes momentum_buf (buf = g', no dampening, as
+// torch clones the gradient).  momentum_buf may be null when momentum == 0 (it is neither read nor written then).
+MOPA_API int mopa_sgd_flat(float* params, const float* grads, float* momentum_buf, int64_t n, float lr, float momentum,
+                           float dampening, float weight_decay, int nesterov, int first, float grad_scale, void* stream) {
+  if (n <= 0 || !params || !grads) return MOPA_ERR_ARG;
+  if (momentum != 0.f && !momentum_buf) return MOPA_ERR_ARG;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) != 0) return MOPA_ERR_ARG;
+  k_sgd_flat<<<stream_grid(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(params, grads, momentum != 0.f ? momentum_buf : nullptr, n, lr,
+                                                                           momentum, dampening, weight_decay, nesterov, first,
+                                                                           grad_scale);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// mopa_sgd_flat behind the step record `rec`.  In place of `first` it takes `buf_valid`, one int32 in DEVICE memory (4-byte
+// aligned; may be null when momentum == 0): 0 = momentum_buf has not been written yet, so the step -- if rec says it is applied --
+// is the first; a second, one-thread launch behind the update then sets it to 1.  A skipped step leaves it, and everything else,
+// alone: the next applied step is still the first.
+MOPA_API int mopa_sgd_flat_guarded(float* params, const float* grads, float* momentum_buf, int64_t n, float lr, float momentum,
+                                   float dampening, float weight_decay, int nesterov, int* buf_valid, float grad_scale,
+                                   const void* rec, void* stream) {
+  if (n <= 0 || !rec || !params || !grads) return MOPA_ERR_ARG;
+  if (momentum != 0.f && (!momentum_buf || !buf_valid)) return MOPA_ERR_ARG;
+  if ((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) != 0) return MOPA_ERR_ARG;
+  if (((uintptr_t)rec & 7) != 0 || ((uintptr_t)buf_valid & 3) != 0) return MOPA_ERR_ARG;
+  const bool use_mom = momentum != 0.f;
+  k_sgd_flat_guarded<<<stream_grid(n / 4 + 1, 256), 256, 0, (hipStream_t)stream>>>(params, grads, use_mom ? momentum_buf : nullptr, n, lr,
+                                                                                   momentum, dampening, weight_decay, nesterov,
+                                                                                   use_mom ? buf_valid : nullptr, grad_scale,
+                                                                                   (const GsStepRec*)rec);
+  MOPA_CHECK_LAUNCH();
+  if (use_mom) {
+    k_sgd_mark_valid<<<1, 64, 0, (hipStream_t)stream>>>(buf_valid, (const GsStepRec*)rec);
+    MOPA_CHECK_LAUNCH();
+  }
   return MOPA_OK;
 }

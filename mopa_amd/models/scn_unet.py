@@ -151,7 +151,7 @@ class UNetSCN(nn.Module):
 def checkpoint_shapes(model: nn.Module):
     """Per trainable parameter of `model` (in ``parameters()`` order): the shape it has in ``state_dict()`` if that differs
     from the live parameter (sparse-conv weights in SparseConvNet's 4-D layout), else ``None``.  For
-    ``FlatAdam(..., checkpoint_shapes=...)``."""
+    ``FlatAdam`` / ``FlatAdamW`` / ``FlatSGD(..., checkpoint_shapes=...)`` (``build_optimizer(..., model_type="3D")`` passes it)."""
     special = {}
     for mod in model.modules():
         if isinstance(mod, _SparseConvParams):

@@ -1,16 +1,20 @@
-"""Flat-buffer Adam + data-parallel gradient all-reduce.
+"""Flat-buffer optimizers (Adam, AdamW, SGD) + data-parallel gradient all-reduce.
 
 All parameters of a network become views into ONE fp32 buffer and their ``.grad`` views into one flat gradient
-buffer: one HIP launch updates the model (``mopa_adam_flat``) and the same flat buffer is what RCCL all-reduces
-over xGMI -- one collective per network per iteration.  Semantics of ``torch.optim.Adam`` as the
-reference configures it (``mopa/common/solver/build.py:7-21``, yaml ``OPTIMIZER: TYPE Adam, BASE_LR 1e-3``).
+buffer: one HIP launch updates the model (``mopa_adam_flat`` / ``mopa_adamw_flat`` / ``mopa_sgd_flat``) and the same flat buffer
+is what RCCL all-reduces over xGMI -- one collective per network per iteration.  The reference builds its optimizer
+as ``getattr(torch.optim, TYPE)`` (``mopa/common/solver/build.py:7-43``) and its config tree names ``Adam`` (yaml
+``OPTIMIZER: TYPE Adam, BASE_LR 1e-3``) and ``SGD`` (``mopa/common/config/base.py:42-70``): ``FlatAdam``, ``FlatAdamW`` and
+``FlatSGD`` have the semantics of the torch class of that name, and ``mopa_amd.common.solver.build.build_optimizer`` picks by
+``TYPE``.  ``FlatOptimizer`` holds what the three share: the buffers, ``all_reduce()`` and the gradient buckets, ``grad_stats()`` and
+the on-device clip / non-finite guard -- so ``FlatEMA``, ``Teacher`` and the bucketed backward work with any of them.
 
-``FlatAdam`` IS a ``torch.optim.Optimizer``: the reference hands its optimizer to ``build_scheduler`` (a
+Each IS a ``torch.optim.Optimizer``: the reference hands its optimizer to ``build_scheduler`` (a
 ``MultiStepLR`` that rewrites ``param_groups[0]["lr"]``, ``mopa/common/solver/build.py:24-47``,
 ``train_xmuda_mopa.py:135-136``) and to ``CheckpointerV2`` which calls ``optimizer.state_dict()`` /
 ``load_state_dict()`` (``mopa/common/utils/checkpoint.py:48-49,76-77``).  ``state_dict()`` has exactly the layout of
-``torch.optim.Adam`` (per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``, one param group), so optimizer
-checkpoints move between the reference and this build in both directions.
+the torch class (Adam / AdamW: per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq``; SGD: per-parameter ``momentum_buffer``; one
+param group), so optimizer checkpoints move between the reference and this build in both directions.
 """
 from __future__ import annotations
 
@@ -38,7 +42,7 @@ class _Works:
 
 
 def stat_chunks(slices, chunk):
-    """The chunk table of ``mopa_grad_stats`` for ``FlatAdam._slices`` (``(offset, numel)`` per parameter): a list of
+    """The chunk table of ``mopa_grad_stats`` for ``FlatOptimizer._slices`` (``(offset, numel)`` per parameter): a list of
     ``(parameter index, lo, hi)`` ranges of the flat buffer, in parameter order.  Every parameter element is in exactly one
     chunk, no chunk crosses a parameter or touches the padding behind one, ``hi - lo <= chunk`` and ``lo % 4 == 0`` (the kernel
     reads a chunk as float4s from ``lo``)."""
@@ -89,44 +93,53 @@ class GradStats:
         return "; ".join(parts)
 
 
-class FlatAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, checkpoint_shapes=None,
-                 max_grad_norm=None, skip_nonfinite=False):
+class FlatOptimizer(torch.optim.Optimizer):
+    """Everything about the flat buffers that is not one update rule: the parameters as views of ONE fp32 buffer ``flat`` and
+    their ``.grad`` as views of ``grad``, the data-parallel ``all_reduce()`` and the gradient buckets, ``grad_stats()`` and the
+    guard's step record, the ``step()`` convention.  A subclass gives
+      * ``_NAME`` (what its messages call it),
+      * ``_update(g, grad_scale, rec)``: enqueue the update kernel, behind the step record ``rec`` when that is not ``None``
+        (``g`` is ``param_groups[0]``),
+      * ``state_dict()`` / ``load_state_dict()`` in the layout of the torch optimizer it stands for."""
+    _NAME = "FlatOptimizer"
+
+    def __init__(self, params, defaults, checkpoint_shapes=None, max_grad_norm=None, skip_nonfinite=False):
         """``checkpoint_shapes``: optional list (one entry per parameter, ``None`` = the parameter's own shape) of the shapes
         the moment tensors take in ``state_dict()`` -- ``mopa_amd.models.scn_unet.checkpoint_shapes(model)`` gives
         SparseConvNet's 4-D conv-weight layout so that a reference-side ``torch.optim.Adam.load_state_dict`` of our
         checkpoint pairs every moment with a parameter of the same shape.
 
-        ``max_grad_norm`` / ``skip_nonfinite`` (the guard; both off by default, and then ``step()`` is the single
-        ``mopa_adam_flat`` launch it always was): with either set, ``step()`` first measures the gradient on the device
+        ``max_grad_norm`` / ``skip_nonfinite`` (the guard; both off by default, and then ``step()`` is the single update launch
+        it always was, ``mopa_adam_flat`` for ``FlatAdam``): with either set, ``step()`` first measures the gradient on the device
         (``mopa_grad_stats``: one read of the flat gradient, per-parameter and total 2-norm of ``grad_scale * g``, max |g|,
-        non-finite count) and then runs ``mopa_adam_flat_guarded``, which takes its decisions from device memory -- no host
-        read, no sync.  ``max_grad_norm``: the update uses ``coef * grad_scale * g`` with ``coef = max_grad_norm / (norm + 1e-6)``
-        clamped to 1, ``torch.nn.utils.clip_grad_norm_``'s formula in float32 (norm type 2).  ``skip_nonfinite``: a step whose
-        gradient holds a NaN or Inf writes nothing -- ``flat``, ``exp_avg`` and ``exp_avg_sq`` keep their bits.  ``last_stats``
-        holds the ``GradStats`` of the last guarded step.  Both are attributes of the optimizer, not ``param_groups`` entries:
-        ``state_dict()`` keeps ``torch.optim.Adam``'s layout.  Differences from torch, on purpose:
+        non-finite count) and then runs the class's guarded kernel (``mopa_adam_flat_guarded``, ``mopa_adamw_flat_guarded``,
+        ``mopa_sgd_flat_guarded``), which takes its decisions from device memory -- no host read, no sync.  ``max_grad_norm``: the
+        update uses ``coef * grad_scale * g`` with ``coef = max_grad_norm / (norm + 1e-6)`` clamped to 1,
+        ``torch.nn.utils.clip_grad_norm_``'s formula in float32 (norm type 2).  ``skip_nonfinite``: a step whose gradient holds a
+        NaN or Inf writes nothing -- ``flat`` and the state buffers (``exp_avg`` / ``exp_avg_sq``, ``momentum_buf``) keep their
+        bits.  ``last_stats`` holds the ``GradStats`` of the last guarded step.  Both are attributes of the optimizer, not
+        ``param_groups`` entries: ``state_dict()`` keeps the torch optimizer's layout.  Differences from torch, on purpose, the
+        same for every class:
           * ``p.grad`` is never modified (``clip_grad_norm_`` rewrites the gradients; here the factor goes into the update);
-          * the step count ``t`` (bias corrections are host scalars) advances on a skipped step too -- torch's fused Adam with
-            ``found_inf`` rolls its device-side step back.  In exchange a guarded optimizer in which nothing triggers is
-            bit-identical to the plain one, at the price of a bias correction a few steps ahead after a skip early in training;
+          * ``FlatAdam`` / ``FlatAdamW``: the step count ``t`` (bias corrections are host scalars) advances on a skipped step too --
+            torch's fused Adam with ``found_inf`` rolls its device-side step back.  In exchange a guarded optimizer in which nothing
+            triggers is bit-identical to the plain one, at the price of a bias correction a few steps ahead after a skip early in
+            training.  (``FlatSGD`` has no step count; its "first step" rule follows the device: see the class);
           * there is no ``error_if_nonfinite`` (it needs a host sync): read ``last_stats.nonfinite`` at the logging period.
         Data parallel: ``step()`` runs after ``all_reduce()`` has been waited for, so every rank measures the same summed buffer
         -- a sum all-reduce leaves identical bits on all ranks -- and takes the same decision; no further collective."""
         params = [p for p in params if p.requires_grad]
         if not params:
-            raise ValueError("FlatAdam got no parameters")
+            raise ValueError("%s got no parameters" % self._NAME)
         if isinstance(params[0], dict):
-            raise ValueError("FlatAdam takes one flat list of parameters (the reference builds a single param group)")
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False))
+            raise ValueError("%s takes one flat list of parameters (the reference builds a single param group)" % self._NAME)
+        super().__init__(params, defaults)
         self.params = params
         dev = params[0].device
         sizes = [(p.numel() + 3) // 4 * 4 for p in params]  # keep every view 16-byte aligned
         self.n = sum(sizes)
         self.flat = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros_like(self.flat)
-        self.exp_avg_sq = torch.zeros_like(self.flat)
         self._slices = []
         off = 0
         with torch.no_grad():
@@ -137,14 +150,13 @@ class FlatAdam(torch.optim.Optimizer):
                 self._slices.append((off, p.numel()))
                 off += sz
         self._attach_grads()
-        self.t = 0
         self.n_collectives = 0        # all-reduces issued so far, and the backend of the last one (bench.py / tests report them)
         self.collective_backend = None
         self._ckpt_shapes = list(checkpoint_shapes) if checkpoint_shapes is not None else [None] * len(params)
         if len(self._ckpt_shapes) != len(params):
             raise ValueError("checkpoint_shapes must have one entry per trainable parameter")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
-            raise ValueError("FlatAdam: max_grad_norm must be positive (None = no clipping)")
+            raise ValueError("%s: max_grad_norm must be positive (None = no clipping)" % self._NAME)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
         self.last_stats = None        # GradStats of the last guarded step()
@@ -183,7 +195,7 @@ class FlatAdam(torch.optim.Optimizer):
                 view.zero_()
             else:               # autograd attached a fresh tensor after the view was dropped: it holds everything accumulated since
                 if g.shape != p.shape:
-                    raise RuntimeError("FlatAdam: a parameter's .grad was replaced by a tensor of another shape")
+                    raise RuntimeError("%s: a parameter's .grad was replaced by a tensor of another shape" % self._NAME)
                 view.copy_(g)
             p.grad = view
 
@@ -274,8 +286,8 @@ class FlatAdam(torch.optim.Optimizer):
         if os.environ.get("MOPA_DIRECT_GRADS", "1") == "0":
             # without in-place gradients autograd's AccumulateGrad adds a pass's gradients to .grad only AFTER Function.backward has
             # returned -- after the bucket's all-reduce would have been enqueued: the collective would race with that add
-            raise RuntimeError("FlatAdam.arm_buckets needs the gradients written in place (MOPA_DIRECT_GRADS=0 is set): "
-                               "use all_reduce() after backward instead")
+            raise RuntimeError("%s.arm_buckets needs the gradients written in place (MOPA_DIRECT_GRADS=0 is set): "
+                               "use all_reduce() after backward instead" % self._NAME)
         self._check_grads()
         self._checked = True
         self._armed = True
@@ -298,7 +310,7 @@ class FlatAdam(torch.optim.Optimizer):
             return
         if id(p) in self._done_ids:
             if self._bucket_issued[b] and not final:
-                raise RuntimeError("FlatAdam buckets: a gradient was written after its bucket's all-reduce had been issued")
+                raise RuntimeError("%s buckets: a gradient was written after its bucket's all-reduce had been issued" % self._NAME)
             return
         self._done_ids.add(id(p))
         self._bucket_left[b] -= 1
@@ -326,7 +338,7 @@ class FlatAdam(torch.optim.Optimizer):
     # ---- gradient statistics and the guarded step (csrc/optim.hip)
     def _grad_stats(self, grad_scale, max_norm, skip_nonfinite, which):
         if self.flat.device.type != "cuda":
-            raise RuntimeError("FlatAdam gradient statistics need the HIP extension on an MI355X (no CPU fallback)")
+            raise RuntimeError("%s gradient statistics need the HIP extension on an MI355X (no CPU fallback)" % self._NAME)
         if self._gs is None:    # once: the chunk table goes up; a (stats, step record) pair and its views for step(), one for grad_stats()
             dev, n_par = self.grad.device, len(self.params)
             tab = torch.tensor(stat_chunks(self._slices, query("mopa_grad_stats_chunk")), dtype=torch.int64).reshape(-1, 3)
@@ -372,21 +384,59 @@ class FlatAdam(torch.optim.Optimizer):
             self._check_grads()
         self._checked = False
         if self.flat.device.type != "cuda":
-            raise RuntimeError("FlatAdam.step needs the HIP extension on an MI355X (no CPU fallback)")
+            raise RuntimeError("%s.step needs the HIP extension on an MI355X (no CPU fallback)" % self._NAME)
         g = self.param_groups[0]
-        b1, b2 = g["betas"]
-        self.t += 1             # on a skipped step too (the bias corrections are host scalars): see __init__
         if self.max_grad_norm is None and not self.skip_nonfinite:
-            call("mopa_adam_flat", ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
-                 float(g["lr"]), b1, b2, g["eps"], g["weight_decay"], 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t),
-                 grad_scale, stream())
+            self._update(g, grad_scale, None)
         else:
             self.last_stats, rec = self._grad_stats(grad_scale, self.max_grad_norm or 0.0, self.skip_nonfinite, "step")
-            call("mopa_adam_flat_guarded", ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n,
-                 float(g["lr"]), b1, b2, g["eps"], g["weight_decay"], 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t),
-                 grad_scale, ptr(rec), stream())
+            self._update(g, grad_scale, rec)
         WEIGHTS_EPOCH[0] += 1   # cached weight re-layouts (dense2d / sparse3d) are stale now (a skipped step rebuilds them unchanged)
         return loss
+
+    def _update(self, g, grad_scale, rec):
+        raise NotImplementedError
+
+    def _state_groups(self):
+        groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+        groups[0]["params"] = list(range(len(self.params)))
+        return groups
+
+    def _load_groups(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
+            raise ValueError("%s.load_state_dict: expected one param group with %d parameters" % (self._NAME, len(self.params)))
+        for k, v in groups[0].items():
+            if k != "params":
+                self.param_groups[0][k] = tuple(v) if k == "betas" else v
+
+
+class FlatAdam(FlatOptimizer):
+    """``torch.optim.Adam`` on the flat buffers (``mopa_adam_flat`` / ``mopa_adam_flat_guarded``); the constructor's arguments
+    beyond torch's are ``FlatOptimizer``'s."""
+    _NAME = "FlatAdam"
+    _KERNEL = "mopa_adam_flat"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, checkpoint_shapes=None,
+                 max_grad_norm=None, skip_nonfinite=False):
+        super().__init__(params, self._defaults(lr, betas, eps, weight_decay), checkpoint_shapes, max_grad_norm, skip_nonfinite)
+        self.exp_avg = torch.zeros_like(self.flat)
+        self.exp_avg_sq = torch.zeros_like(self.flat)
+        self.t = 0
+
+    @staticmethod
+    def _defaults(lr, betas, eps, weight_decay):
+        return dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False)
+
+    def _update(self, g, grad_scale, rec):
+        b1, b2 = g["betas"]
+        self.t += 1             # on a skipped step too (the bias corrections are host scalars): see FlatOptimizer.__init__
+        args = (ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.n, float(g["lr"]), b1, b2, g["eps"],
+                g["weight_decay"], 1.0 - b1 ** self.t, math.sqrt(1.0 - b2 ** self.t), grad_scale)
+        if rec is None:
+            call(self._KERNEL, *args, stream())
+        else:
+            call(self._KERNEL + "_guarded", *args, ptr(rec), stream())
 
     # ---- checkpointing in torch.optim.Adam's layout (mopa/common/utils/checkpoint.py:48-49,76-77)
     def state_dict(self):
@@ -397,17 +447,10 @@ class FlatAdam(torch.optim.Optimizer):
                 state[i] = {"step": torch.tensor(float(self.t)),
                             "exp_avg": self.exp_avg[off:off + n].view(shape).clone(),
                             "exp_avg_sq": self.exp_avg_sq[off:off + n].view(shape).clone()}
-        groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
-        groups[0]["params"] = list(range(len(self.params)))
-        return {"state": state, "param_groups": groups}
+        return {"state": state, "param_groups": self._state_groups()}
 
     def load_state_dict(self, sd):
-        groups = sd["param_groups"]
-        if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
-            raise ValueError("FlatAdam.load_state_dict: expected one param group with %d parameters" % len(self.params))
-        for k, v in groups[0].items():
-            if k != "params":
-                self.param_groups[0][k] = tuple(v) if k == "betas" else v
+        self._load_groups(sd)
         steps = set()
         self.exp_avg.zero_()
         self.exp_avg_sq.zero_()
@@ -418,5 +461,101 @@ class FlatAdam(torch.optim.Optimizer):
             self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
             steps.add(int(float(st["step"])))
         if len(steps) > 1:
-            raise ValueError("FlatAdam.load_state_dict: parameters with different step counts (one fused update per model)")
+            raise ValueError("%s.load_state_dict: parameters with different step counts (one fused update per model)" % self._NAME)
         self.t = steps.pop() if steps else 0
+
+
+def _torch_defaults(cls, **kw):
+    """The ``defaults`` the installed ``torch.optim`` class makes of these arguments (its own argument checks and messages, and
+    every key its ``state_dict()`` saves in a param group), taken from an instance over one scalar parameter."""
+    return dict(cls([torch.zeros((), requires_grad=True)], **kw).defaults)
+
+
+class FlatAdamW(FlatAdam):
+    """``torch.optim.AdamW`` on the flat buffers (``mopa_adamw_flat`` / ``mopa_adamw_flat_guarded``): ``p *= 1 - lr * weight_decay``,
+    then Adam's update with no L2 term in the gradient.  The state -- and with it ``state_dict()`` / ``load_state_dict()`` and the
+    step count's behaviour on a skipped step -- is ``FlatAdam``'s; the param group carries what the installed ``torch.optim.AdamW``
+    saves."""
+    _NAME = "FlatAdamW"
+    _KERNEL = "mopa_adamw_flat"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, checkpoint_shapes=None,
+                 max_grad_norm=None, skip_nonfinite=False):
+        super().__init__(params, lr, betas, eps, weight_decay, checkpoint_shapes, max_grad_norm, skip_nonfinite)
+
+    @staticmethod
+    def _defaults(lr, betas, eps, weight_decay):
+        return _torch_defaults(torch.optim.AdamW, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+
+
+class FlatSGD(FlatOptimizer):
+    """``torch.optim.SGD`` on the flat buffers (``mopa_sgd_flat`` / ``mopa_sgd_flat_guarded``), element for element:
+    ``g' = grad_scale g + wd p``; ``buf = g'`` on the first applied step (no dampening: torch clones the gradient), afterwards
+    ``buf = momentum buf + (1 - dampening) g'``; ``p -= lr (g' + momentum buf | buf | g')`` (nesterov | momentum | neither).
+    The param-group keys are those of the installed ``torch.optim.SGD``, its argument errors too (Nesterov needs a momentum and
+    zero dampening).  ``momentum_buf`` is one flat buffer beside ``flat`` (``None`` while ``momentum == 0``).
+
+    Which step is the first: without the guard the host knows (``_first``).  With ``skip_nonfinite`` it cannot -- whether step 1
+    was applied is decided on the device -- so the guarded kernel reads one int32 of device memory, ``_valid`` (0 until a step has
+    been applied; set behind the update, on the same stream, when the step record says applied): a skipped first step leaves the
+    next one "first".  The word is read back in ``state_dict()`` only (and once if the guard is switched off in mid-training)."""
+    _NAME = "FlatSGD"
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, checkpoint_shapes=None,
+                 max_grad_norm=None, skip_nonfinite=False):
+        defaults = _torch_defaults(torch.optim.SGD, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                   nesterov=nesterov)
+        super().__init__(params, defaults, checkpoint_shapes, max_grad_norm, skip_nonfinite)
+        self.momentum_buf = torch.zeros_like(self.flat) if momentum != 0 else None
+        self._first = True            # host side: True / False, None = a guarded step has run since and only _valid knows
+        self._valid = torch.zeros(1, dtype=torch.int32, device=self.flat.device)
+
+    def _buf_written(self):
+        if self._first is None:
+            self._first = int(self._valid) == 0
+        return not self._first
+
+    def _update(self, g, grad_scale, rec):
+        mom = float(g["momentum"])
+        if mom != 0.0 and self.momentum_buf is None:     # momentum switched on through param_groups after construction
+            self.momentum_buf = torch.zeros_like(self.flat)
+        head = (ptr(self.flat), ptr(self.grad), ptr(self.momentum_buf) if mom != 0.0 else None, self.n, float(g["lr"]), mom,
+                float(g["dampening"]), float(g["weight_decay"]), int(bool(g["nesterov"])))
+        if rec is None:
+            first = not self._buf_written()
+            call("mopa_sgd_flat", *head, int(first), grad_scale, stream())
+            if first and mom != 0.0:
+                self._first = False
+                self._valid.fill_(1)
+        else:
+            call("mopa_sgd_flat_guarded", *head, ptr(self._valid), grad_scale, ptr(rec), stream())
+            if self._first and mom != 0.0:
+                self._first = None
+
+    # ---- checkpointing in torch.optim.SGD's layout: per-parameter `momentum_buffer`, nothing before the first applied step,
+    # nothing at all without momentum
+    def state_dict(self):
+        state = {}
+        if self.momentum_buf is not None and self.param_groups[0]["momentum"] != 0 and self._buf_written():
+            for i, (off, n) in enumerate(self._slices):
+                shape = self._ckpt_shapes[i] or self.params[i].shape
+                state[i] = {"momentum_buffer": self.momentum_buf[off:off + n].view(shape).clone()}
+        return {"state": state, "param_groups": self._state_groups()}
+
+    def load_state_dict(self, sd):
+        self._load_groups(sd)
+        bufs = {int(k): st["momentum_buffer"] for k, st in sd["state"].items() if st.get("momentum_buffer") is not None}
+        if self.param_groups[0]["momentum"] == 0:
+            bufs = {}
+        if bufs and len(bufs) != len(self.params):
+            raise ValueError("FlatSGD.load_state_dict: momentum buffers for %d of %d parameters (one fused update per model)"
+                             % (len(bufs), len(self.params)))
+        if self.param_groups[0]["momentum"] != 0 and self.momentum_buf is None:
+            self.momentum_buf = torch.zeros_like(self.flat)
+        if self.momentum_buf is not None:
+            self.momentum_buf.zero_()
+        for i, t in bufs.items():
+            off, n = self._slices[i]
+            self.momentum_buf[off:off + n].copy_(t.reshape(-1))
+        self._first = not bufs        # loaded buffers mean "not first"
+        self._valid.fill_(0 if self._first else 1)

@@ -3,7 +3,7 @@
 
 * ``refine_pseudo_labels(probs, pseudo_label)``  == ``mopa/data/utils/refine_pseudo_labels.py:5-22`` on device tensors;
 * ``pseudo_labels(logit_2d, logit_3d, xm)``      == softmax -> (entropy-weighted fusion) -> max/argmax -> refine;
-* ``FlatEMA(optimizer, decay)``                  == ``torch_ema.ExponentialMovingAverage`` over a ``FlatAdam`` buffer
+* ``FlatEMA(optimizer, decay)``                  == ``torch_ema.ExponentialMovingAverage`` over a flat optimizer's buffer
   (``update()``, ``average_parameters()`` context manager).
 """
 from __future__ import annotations
@@ -59,7 +59,8 @@ def pseudo_labels(logit_2d: torch.Tensor, logit_3d: torch.Tensor, xm: bool, igno
 
 
 class FlatEMA:
-    """Exponential moving average of a network's weights, kept as one flat buffer beside ``FlatAdam``'s."""
+    """Exponential moving average of a network's weights, kept as one flat buffer beside the optimizer's (any ``mopa_amd.optim.FlatOptimizer``:
+    ``FlatAdam``, ``FlatAdamW``, ``FlatSGD``)."""
 
     def __init__(self, optimizer, decay: float, use_num_updates: bool = True):
         self.opt, self.decay = optimizer, float(decay)
@@ -70,7 +71,7 @@ class FlatEMA:
     def state_dict(self):
         """Same keys as ``torch_ema.ExponentialMovingAverage.state_dict()`` (per-parameter shadow tensors), so EMA
         checkpoints written by the reference's ``CheckpointerV2(..., ema=...)`` style code load here and vice versa.  The
-        shadow tensors take the optimizer's checkpoint shapes (SparseConvNet's 4-D conv-weight layout when ``FlatAdam`` was built
+        shadow tensors take the optimizer's checkpoint shapes (SparseConvNet's 4-D conv-weight layout when the optimizer was built
         with ``checkpoint_shapes``), i.e. the shapes ``model.state_dict()`` saves -- a reference-side ``copy_to`` then pairs every
         shadow tensor with a parameter of its own shape."""
         shapes = getattr(self.opt, "_ckpt_shapes", [None] * len(self.opt.params))
