@@ -78,6 +78,13 @@ SECTIONS = [
  * refine_pseudo_labels (mopa/data/utils/refine_pseudo_labels.py:5-22) for many (array, scan) segments at once; same bits as
  * mopa_rotate_points_f32 + mopa_voxelize per scan.  Per-scan pointers, sizes and draws are small host arrays (at most 32 scans,
  * 64 segments per call)."""),
+    ("kittiprep.hip", """SemanticKITTI's on-the-fly projection on the device, all scans of an iteration per launch: the z > -3 filter, the low 16
+ * label bits, the ground mask from PatchWork++'s index list, the front-half filter, proj_matrix times the homogeneous points (per
+ * row the fused chain fma(m3, 1, fma(m2, z, fma(m1, y, m0 * x)))), the perspective divide, np.around(., 2), the strict frustum
+ * test and one ordered compaction of every per-point array -- data_extraction and preprocess of
+ * mopa/data/semantic_kitti/semantic_kitti_dataloader.py:349-371,422-507 with select_points_in_frustum (:236-252); the pseudo-label
+ * form (:430-469) takes the loaded keep mask instead of projecting.  Per-scan pointers and matrices are small host arrays (at most
+ * 32 scans per call); the caller reads back the 2 B counts once, between mopa_kittiprep_count and mopa_kittiprep_scatter."""),
     ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3).
  * Not in the reference (opt-in): mopa_grad_stats = per-parameter and total 2-norm, max |g| and non-finite count of the flat gradient
  * (what torch.nn.utils.clip_grad_norm_ and torch.isfinite would compute, without a host read), mopa_adam_flat_guarded = the same
