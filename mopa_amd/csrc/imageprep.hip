@@ -3,12 +3,14 @@
 //
 // Reference: the per-sample work of Dataset.__getitem__ (mopa/data/nuscenes/nuscenes_dataloader.py:347-408,
 // mopa/data/a2d2/a2d2_dataloader.py:237-263, mopa/data/semantic_kitti/semantic_kitti_dataloader.py:563-630) and refine_sam_mask
-// (mopa/data/utils/refine_pseudo_labels.py:72-102): Pillow's BILINEAR resize of 8-bit images, ImageEnhance's three blends behind
-// torchvision's ColorJitter, scipy.ndimage.zoom(order=0), np.fliplr, /255. and the normalisation.  Fixture: G10.
+// (mopa/data/utils/refine_pseudo_labels.py:72-102): Pillow's BILINEAR resize of 8-bit images, ImageEnhance's three blends and the
+// HSV round trip of adjust_hue behind torchvision's ColorJitter, scipy.ndimage.zoom(order=0), np.fliplr, /255. and the
+// normalisation.  Fixtures: G10, G14 (hue).
 //
 // Everything is exact: the resize is integer multiply-adds on host-built 22-bit coefficient tables (the horizontal pass rounds to
 // uint8 before the vertical one, as Pillow's two passes do), the blends are float32 with every product and sum rounded on its
-// own (no contraction), the contrast mean and the mask's per-id areas are integer sums.  No float atomics.
+// own (no contraction), the hue step keeps Pillow's mix of float32 and double (ip_hue), the contrast mean and the mask's per-id
+// areas are integer sums.  No float atomics.
 //
 // B images of one size go through a stage in ONE launch (blockIdx.z = image); the per-image pointers and draws are small host
 // arrays copied into the kernel arguments, so nothing is uploaded and nothing synchronises.  3-byte pixels are read as aligned
@@ -28,8 +30,9 @@
 
 struct IpSrc { const uint8_t* p[IP_MAXB]; };
 struct IpJitter {
-  int8_t order[IP_MAXB][3];   // 0 brightness, 1 contrast, 2 saturation, -1 = end of list
-  float factor[IP_MAXB][3];   // factor of order[j]
+  int8_t order[IP_MAXB][4];   // 0 brightness, 1 contrast, 2 saturation, 3 hue, -1 = end of list
+  float factor[IP_MAXB][4];   // factor of order[j] (unused for hue)
+  uint8_t shift[IP_MAXB];     // hue: what is added to H modulo 256
   uint8_t flip[IP_MAXB];
 };
 
@@ -169,14 +172,64 @@ __device__ __forceinline__ int ip_blend(int deg, int v, float f, bool inside) {
 }
 __device__ __forceinline__ int ip_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
 
+// torchvision's adjust_hue on a PIL image: Pillow's rgb2hsv, H = (H + shift) & 255, Pillow's hsv2rgb (Convert.c).  The round trip
+// is lossy and is made for shift 0 too.  Pillow's widths are kept: rgb2hsv takes its quotients in float32, evaluates the three-way
+// hue expression in double and stores it to float32; hsv2rgb stores f and fs to float32, takes fs * f as a float32 product and
+// everything else in double.  fmod(x, 1.0) of an x in (0, 2) is x - floor(x), exactly; C's round() of these non-negative
+// values is floor(x + 0.5).
+__device__ __forceinline__ void ip_hue(int shift, int& r, int& g, int& b) {
+  const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
+  const int V = maxc;
+  int H = 0, S = 0;
+  if (maxc != minc) {
+    const float cr = (float)(maxc - minc);
+    const float s = __fdiv_rn(cr, (float)maxc);
+    S = ip_clip8((int)((double)s * 255.0));
+    const double rc = (double)__fdiv_rn((float)(maxc - r), cr), gc = (double)__fdiv_rn((float)(maxc - g), cr),
+                 bc = (double)__fdiv_rn((float)(maxc - b), cr);
+    float h;
+    if (r == maxc) h = (float)(bc - gc);
+    else if (g == maxc) h = (float)(2.0 + rc - bc);
+    else h = (float)(4.0 + gc - rc);
+    const double x = (double)h / 6.0 + 1.0;
+    h = (float)(x - floor(x));
+    H = ip_clip8((int)((double)h * 255.0));
+  }
+  H = (H + shift) & 255;
+  if (S == 0) {
+    r = g = b = V;
+    return;
+  }
+  const double h6 = (double)H * 6.0 / 255.0, fi = floor(h6);
+  const float f = (float)(h6 - fi);
+  const float fs = (float)((double)S / 255.0);
+  const float fsf = fs * f;
+  const double v = (double)V;
+  const int p = ip_clip8((int)floor(v * (1.0 - (double)fs) + 0.5));
+  const int q = ip_clip8((int)floor(v * (1.0 - (double)fsf) + 0.5));
+  const int t = ip_clip8((int)floor(v * (1.0 - (double)fs * (1.0 - (double)f)) + 0.5));
+  switch ((int)fi % 6) {                                   // H = 255 gives fi = 6
+    case 0: r = V, g = t, b = p; break;
+    case 1: r = q, g = V, b = p; break;
+    case 2: r = p, g = V, b = t; break;
+    case 3: r = p, g = q, b = V; break;
+    case 4: r = t, g = p, b = V; break;
+    default: r = V, g = p, b = q; break;
+  }
+}
+
 // Applies order[] to (r, g, b); `until_contrast` stops in front of the contrast step and reports whether there is one.
-__device__ __forceinline__ bool ip_jitter(const int8_t* order, const float* factor, int mean, bool until_contrast, int& r, int& g,
-                                          int& b) {
+__device__ __forceinline__ bool ip_jitter(const int8_t* order, const float* factor, int shift, int mean, bool until_contrast, int& r,
+                                          int& g, int& b) {
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
+  for (int j = 0; j < 4; ++j) {
     const int op = order[j];
     if (op < 0) break;
     if (op == 1 && until_contrast) return true;
+    if (op == 3) {
+      ip_hue(shift, r, g, b);
+      continue;
+    }
     const float f = factor[j];
     const bool inside = f >= 0.f && f <= 1.f;
     const int l = ip_luma(r, g, b);
@@ -189,10 +242,11 @@ __device__ __forceinline__ bool ip_jitter(const int8_t* order, const float* fact
 }
 
 __device__ __forceinline__ bool ip_has_contrast(const int8_t* order) {
-  return order[0] == 1 || (order[0] >= 0 && (order[1] == 1 || (order[1] >= 0 && order[2] == 1)));
+  return order[0] == 1 || (order[0] >= 0 && (order[1] == 1 || (order[1] >= 0 && (order[2] == 1 || (order[2] >= 0 && order[3] == 1)))));
 }
 
-// sums[b] += sum of L over the image as it stands in front of its contrast step (integer: exact in any order)
+// sums[b] += sum of L over the image as it stands in front of its contrast step, a hue step before it included (integer: exact
+// in any order)
 __global__ __launch_bounds__(IP_BLOCK) void k_contrast_sums(IpSrc src, int64_t pitch, int h, int w, IpJitter jit,
                                                             unsigned long long* __restrict__ sums) {
   __shared__ __align__(16) uint32_t row[(IP_BLOCK * 3 + 8) / 4 + 1];
@@ -208,7 +262,7 @@ __global__ __launch_bounds__(IP_BLOCK) void k_contrast_sums(IpSrc src, int64_t p
     if ((int)threadIdx.x < nxs) {
       const uint8_t* p = reinterpret_cast<const uint8_t*>(row) + s + 3 * threadIdx.x;
       int r = p[0], g = p[1], bl = p[2];
-      ip_jitter(jit.order[b], jit.factor[b], 0, true, r, g, bl);
+      ip_jitter(jit.order[b], jit.factor[b], jit.shift[b], 0, true, r, g, bl);
       acc += ip_luma(r, g, bl);                                            // <= 255 per row: no overflow below 2^23 rows
     }
   }
@@ -246,7 +300,7 @@ __global__ __launch_bounds__(IP_BLOCK) void k_pixels(IpSrc src, int64_t pitch, i
       o[plane] = __fdiv_rn((float)g, 255.f);
       o[2 * plane] = __fdiv_rn((float)bl, 255.f);
     }
-    ip_jitter(jit.order[b], jit.factor[b], mean, false, r, g, bl);
+    ip_jitter(jit.order[b], jit.factor[b], jit.shift[b], mean, false, r, g, bl);
     if (dst_f32) {
       float f0 = __fdiv_rn((float)r, 255.f), f1 = __fdiv_rn((float)g, 255.f), f2 = __fdiv_rn((float)bl, 255.f);
       if (normalise) {
@@ -273,38 +327,42 @@ __global__ __launch_bounds__(IP_BLOCK) void k_pixels(IpSrc src, int64_t pitch, i
   }
 }
 
-static int ip_fill(const void* const* src_host, int B, const int32_t* order_host, const float* factor_host,
-                   const int32_t* flip_host, IpSrc& s, IpJitter& j) {
+// `slots` operations per image in order_host / factor_host: 3 (brightness, contrast, saturation only) or 4 (hue too, with its
+// shift in shift_host[b]); the slots a three-slot caller does not have are filled with -1.
+static int ip_fill(const void* const* src_host, int B, int slots, const int32_t* order_host, const float* factor_host,
+                   const int32_t* shift_host, const int32_t* flip_host, IpSrc& s, IpJitter& j) {
   if (!src_host || B < 1 || B > IP_MAXB) return MOPA_ERR_ARG;
   for (int b = 0; b < B; ++b) {
     if (!src_host[b]) return MOPA_ERR_ARG;
     s.p[b] = (const uint8_t*)src_host[b];
     unsigned seen = 0;
     bool ended = false;
-    for (int k = 0; k < 3; ++k) {
-      const int op = order_host ? order_host[3 * b + k] : -1;
-      if (op < -1 || op > 2) return MOPA_ERR_ARG;
+    const int shift = shift_host ? shift_host[b] : 0;
+    if (shift < 0 || shift > 255) return MOPA_ERR_ARG;
+    j.shift[b] = (uint8_t)shift;
+    for (int k = 0; k < 4; ++k) {
+      const int op = (order_host && k < slots) ? order_host[slots * b + k] : -1;
+      if (op < -1 || op >= slots) return MOPA_ERR_ARG;
       if (op < 0) ended = true;
       else if (ended || (seen & (1u << op))) return MOPA_ERR_ARG;         // each operation at most once, no gaps
       else seen |= 1u << op;
-      if (op >= 0 && !factor_host) return MOPA_ERR_ARG;
+      if (op == 3 && !shift_host) return MOPA_ERR_ARG;
+      const bool blend = op >= 0 && op <= 2;
+      if (blend && !factor_host) return MOPA_ERR_ARG;
       j.order[b][k] = (int8_t)op;
-      j.factor[b][k] = (op >= 0) ? factor_host[3 * b + k] : 1.f;
-      if (op >= 0 && !(j.factor[b][k] == j.factor[b][k])) return MOPA_ERR_ARG;
+      j.factor[b][k] = blend ? factor_host[slots * b + k] : 1.f;
+      if (blend && !(j.factor[b][k] == j.factor[b][k])) return MOPA_ERR_ARG;
     }
     j.flip[b] = (flip_host && flip_host[b]) ? 1 : 0;
   }
   return MOPA_OK;
 }
 
-// sums: B x uint64, zeroed here.  pitch: bytes between rows of the (possibly cropped) h x w window src_host[b] points at.
-// order_host: B x 3 operations in the order they are applied (0 brightness, 1 contrast, 2 saturation, -1 = none left), each at
-// most once; factor_host: B x 3, the factor of order_host[b][j].
-MOPA_API int mopa_imageprep_contrast_sums(const void* const* src_host, int B, int64_t pitch, int h, int w,
-                                          const int32_t* order_host, const float* factor_host, void* sums, void* stream) {
+static int ip_contrast_sums(const void* const* src_host, int B, int64_t pitch, int h, int w, int slots, const int32_t* order_host,
+                            const float* factor_host, const int32_t* shift_host, void* sums, void* stream) {
   IpSrc s;
   IpJitter j;
-  if (ip_fill(src_host, B, order_host, factor_host, nullptr, s, j) != MOPA_OK) return MOPA_ERR_ARG;
+  if (ip_fill(src_host, B, slots, order_host, factor_host, shift_host, nullptr, s, j) != MOPA_OK) return MOPA_ERR_ARG;
   if (h < 1 || w < 1 || pitch < (int64_t)w * 3 || !sums || (int64_t)h * w > ((int64_t)1 << 31)) return MOPA_ERR_ARG;
   if (hipMemsetAsync(sums, 0, 8 * (size_t)B, (hipStream_t)stream) != hipSuccess) return MOPA_ERR_LAUNCH;
   dim3 grid((w + IP_BLOCK - 1) / IP_BLOCK, min(h, 64), B);
@@ -313,18 +371,16 @@ MOPA_API int mopa_imageprep_contrast_sums(const void* const* src_host, int B, in
   return MOPA_OK;
 }
 
-// dst_u8 (B, h, w, 3) and / or dst_f32 (B, 3, h, w); norm_host = {mean[3], std[3]} or null; ori (B, 3, h, w) or null: the
-// unjittered, unflipped /255. copy.  sums: what mopa_imageprep_contrast_sums wrote (null when no image has a contrast step).
-MOPA_API int mopa_imageprep_pixels(const void* const* src_host, int B, int64_t pitch, int h, int w, const int32_t* order_host,
-                                   const float* factor_host, const void* sums, const int32_t* flip_host, uint8_t* dst_u8,
-                                   float* dst_f32, const float* norm_host, float* ori, void* stream) {
+static int ip_pixels(const void* const* src_host, int B, int64_t pitch, int h, int w, int slots, const int32_t* order_host,
+                     const float* factor_host, const int32_t* shift_host, const void* sums, const int32_t* flip_host,
+                     uint8_t* dst_u8, float* dst_f32, const float* norm_host, float* ori, void* stream) {
   IpSrc s;
   IpJitter j;
-  if (ip_fill(src_host, B, order_host, factor_host, flip_host, s, j) != MOPA_OK) return MOPA_ERR_ARG;
+  if (ip_fill(src_host, B, slots, order_host, factor_host, shift_host, flip_host, s, j) != MOPA_OK) return MOPA_ERR_ARG;
   if (h < 1 || w < 1 || h > 65535 || pitch < (int64_t)w * 3 || (!dst_u8 && !dst_f32)) return MOPA_ERR_ARG;
   for (int b = 0; b < B; ++b) {
     bool contrast = false;
-    for (int k = 0; k < 3; ++k) contrast |= j.order[b][k] == 1;
+    for (int k = 0; k < 4; ++k) contrast |= j.order[b][k] == 1;
     if (contrast && !sums) return MOPA_ERR_ARG;
   }
   float n[6] = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f};
@@ -335,6 +391,40 @@ MOPA_API int mopa_imageprep_pixels(const void* const* src_host, int B, int64_t p
                      dst_u8, dst_f32, norm_host ? 1 : 0, n[0], n[1], n[2], n[3], n[4], n[5], ori);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
+}
+
+// sums: B x uint64, zeroed here.  pitch: bytes between rows of the (possibly cropped) h x w window src_host[b] points at.
+// order_host: B x 3 operations in the order they are applied (0 brightness, 1 contrast, 2 saturation, -1 = none left), each at
+// most once; factor_host: B x 3, the factor of order_host[b][j].
+MOPA_API int mopa_imageprep_contrast_sums(const void* const* src_host, int B, int64_t pitch, int h, int w,
+                                          const int32_t* order_host, const float* factor_host, void* sums, void* stream) {
+  return ip_contrast_sums(src_host, B, pitch, h, w, 3, order_host, factor_host, nullptr, sums, stream);
+}
+
+// dst_u8 (B, h, w, 3) and / or dst_f32 (B, 3, h, w); norm_host = {mean[3], std[3]} or null; ori (B, 3, h, w) or null: the
+// unjittered, unflipped /255. copy.  sums: what mopa_imageprep_contrast_sums wrote (null when no image has a contrast step).
+MOPA_API int mopa_imageprep_pixels(const void* const* src_host, int B, int64_t pitch, int h, int w, const int32_t* order_host,
+                                   const float* factor_host, const void* sums, const int32_t* flip_host, uint8_t* dst_u8,
+                                   float* dst_f32, const float* norm_host, float* ori, void* stream) {
+  return ip_pixels(src_host, B, pitch, h, w, 3, order_host, factor_host, nullptr, sums, flip_host, dst_u8, dst_f32, norm_host, ori,
+                   stream);
+}
+
+// The same two with the fourth operation: order_host and factor_host are B x 4, operation 3 = hue (torchvision's adjust_hue on a
+// PIL image); its factor slot is not read, shift_host[b] = int(hue_factor * 255) mod 256, in 0..255, is what is added to H.  The
+// sums are taken of the image in front of its contrast step, a hue step before it applied.
+MOPA_API int mopa_imageprep_contrast_sums4(const void* const* src_host, int B, int64_t pitch, int h, int w,
+                                           const int32_t* order_host, const float* factor_host, const int32_t* shift_host,
+                                           void* sums, void* stream) {
+  return ip_contrast_sums(src_host, B, pitch, h, w, 4, order_host, factor_host, shift_host, sums, stream);
+}
+
+MOPA_API int mopa_imageprep_pixels4(const void* const* src_host, int B, int64_t pitch, int h, int w, const int32_t* order_host,
+                                    const float* factor_host, const int32_t* shift_host, const void* sums,
+                                    const int32_t* flip_host, uint8_t* dst_u8, float* dst_f32, const float* norm_host, float* ori,
+                                    void* stream) {
+  return ip_pixels(src_host, B, pitch, h, w, 4, order_host, factor_host, shift_host, sums, flip_host, dst_u8, dst_f32, norm_host,
+                   ori, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ 4. SAM mask

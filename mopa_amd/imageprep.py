@@ -2,13 +2,14 @@
 iteration -> ``img`` (B,3,h,w) float32, ``sam_mask_ls`` (int32, -100 = ignore) and ``img_indices`` (int64), the 2D side of the
 reference's collate layout (``mopa/data/collate.py:125-278``), ready for ``Net2DSeg.forward`` and ``mask_cons_loss``.
 
-Mirrors, bit for bit (fixture G10, produced by running Pillow, scipy and the reference's ``refine_sam_mask``), what the datasets do
+Mirrors, bit for bit (fixtures G10 and G14, produced by running Pillow, scipy and the reference's ``refine_sam_mask``), what the datasets do
 per sample on the host in ``__getitem__`` (``mopa/data/nuscenes/nuscenes_dataloader.py:347-408``, ``a2d2_dataloader.py:237-263``,
 ``semantic_kitti_dataloader.py:563-630``):
 
 1. ``resize_bilinear_u8``  ``Image.resize(size, Image.BILINEAR)`` of an 8-bit image -- or, for SemanticKITTI, a crop WINDOW
    ``(left, top, right, bottom)`` that the later stages read through (``image.crop``; no copy is made).
-2. ``color_jitter_u8``     ``T.ColorJitter(b, c, s)`` on a PIL image = ``ImageEnhance.{Brightness, Contrast, Color}`` in a drawn order.
+2. ``color_jitter_u8``     ``T.ColorJitter(b, c, s, h)`` on a PIL image = ``ImageEnhance.{Brightness, Contrast, Color}`` and
+   ``adjust_hue`` (Pillow's RGB -> HSV, ``H += int(factor * 255)`` modulo 256, HSV -> RGB) in a drawn order.
 3. ``to_tensor``           ``np.fliplr``, ``np.array(image, float32) / 255.``, ``(image - mean) / std``, ``np.moveaxis(image, -1, 0)``;
    with ``ori=True`` also the unjittered, unflipped ``/ 255.`` copy (``ori_img`` of ``ema_input``).
 4. ``prepare_sam_mask``    ``scipy.ndimage.zoom(mask, 0.25, order=0)`` + ``refine_sam_mask`` (``refine_pseudo_labels.py:72-102``) + crop + flip.
@@ -20,7 +21,7 @@ generators); the device part is deterministic.  There is no CPU fallback and -- 
 the kernels (``csrc/imageprep.hip``) run on the current stream.
 
 Deviations: the datasets' ``assert`` that every index lies inside the image is not made (it would need a
-host sync; ``Net2DSeg`` checks the indices it is given); hue jitter is not built (every shipped config has it off).
+host sync; ``Net2DSeg`` checks the indices it is given).
 """
 from __future__ import annotations
 
@@ -35,7 +36,7 @@ from ._lib import call, chunk_ranges, host_addr, host_i32, host_ptrs, ptr, query
 MAXB = 32                       # csrc/imageprep.hip IP_MAXB: images per launch
 PRECISION_BITS = 22             # Pillow: 32 - 8 - 2
 _TILE = 128                     # csrc/imageprep.hip IP_RS_TW
-BRIGHTNESS, CONTRAST, SATURATION = 0, 1, 2
+BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
 
 
 # ------------------------------------------------------------------------------------------------ host tables
@@ -115,19 +116,49 @@ def draw_bottom_crop(image_size, bottom_crop):
     return (left, image_size[1] - bottom_crop[1], left + bottom_crop[0], image_size[1])
 
 
-def draw_color_jitter(brightness=0.4, contrast=0.4, saturation=0.4):
-    """The draws of ``torchvision.transforms.ColorJitter(brightness, contrast, saturation)`` for one image, from torch's global
+def _hue_range(hue):
+    """torchvision's ``ColorJitter._check_input(hue, "hue", center=0, bound=(-0.5, 0.5), clip_first_on_zero=False)``: the
+    ``(lo, hi)`` to draw from, or None when the range is (0, 0) and hue is off.  Every refusal is a ``ValueError`` in
+    torchvision's words (torchvision raises ``TypeError`` for a value that is neither a number nor a pair)."""
+    if isinstance(hue, (int, float)) and not isinstance(hue, bool):
+        if hue < 0:
+            raise ValueError("If hue is a single number, it must be non negative.")
+        rng = [-float(hue), float(hue)]
+    elif isinstance(hue, (tuple, list)) and len(hue) == 2:
+        rng = [float(hue[0]), float(hue[1])]
+    else:
+        raise ValueError("hue should be a single number or a list/tuple with length 2.")
+    if not -0.5 <= rng[0] <= rng[1] <= 0.5:
+        raise ValueError(f"hue values should be between (-0.5, 0.5), but got {rng}.")
+    return None if rng[0] == rng[1] == 0 else tuple(rng)
+
+
+def hue_shift(factor) -> int:
+    """What ``adjust_hue`` adds to H: ``np.int32(hue_factor * 255).astype(np.uint8)`` -- the product in double of the float32
+    the draw produced, truncated toward zero, modulo 256."""
+    f = float(np.float32(factor))
+    if not -0.5 <= f <= 0.5:
+        raise ValueError(f"hue_factor ({f}) is not in [-0.5, 0.5].")
+    return int(f * 255) & 255
+
+
+def draw_color_jitter(brightness=0.4, contrast=0.4, saturation=0.4, hue=0.0):
+    """The draws of ``torchvision.transforms.ColorJitter(brightness, contrast, saturation, hue)`` for one image, from torch's global
     generator: ``torch.randperm(4)`` for the order of (brightness, contrast, saturation, hue), then one
-    ``torch.empty(1).uniform_(max(0, 1 - v), 1 + v)`` per switched-on operation in that fixed order (hue is off: no draw).
+    ``torch.empty(1).uniform_(max(0, 1 - v), 1 + v)`` per switched-on operation in that fixed order; hue last, from ``(-h, h)`` for
+    a float ``0 <= h <= 0.5`` or from a pair inside ``[-0.5, 0.5]`` (anything else is torchvision's ``ValueError``; 0: no draw).
     Returns ``(order, factors)``: the operations in the order they are applied and their factors.
 
     NOT VERIFIED against torchvision, which is not installed where this was written: ``get_params`` is restated from knowledge
     (DESIGN.md section 4).  The deterministic stages do not depend on it."""
+    hue_range = _hue_range(hue)
     perm = torch.randperm(4).tolist()
     factor = {}
     for op, v in ((BRIGHTNESS, brightness), (CONTRAST, contrast), (SATURATION, saturation)):
         if v:
             factor[op] = float(torch.empty(1).uniform_(max(0.0, 1.0 - v), 1.0 + v))
+    if hue_range is not None:
+        factor[HUE] = float(torch.empty(1).uniform_(hue_range[0], hue_range[1]))
     order = tuple(op for op in perm if op in factor)
     return order, tuple(factor[op] for op in order)
 
@@ -167,23 +198,26 @@ def _on_gpu(items, what="images"):
 
 
 def _jitter_tables(jitter, B):
-    """list of (order, factors) or None per image -> (int32[B][3], float[B][3]) host arrays; (None, None) when nothing is on."""
+    """list of (order, factors) or None per image -> (int32[B][4], float[B][4], int32[B] hue shifts) host arrays; three times
+    None when nothing is on."""
     if jitter is None or all(j is None or len(j[0]) == 0 for j in jitter):
-        return None, None
+        return None, None, None
     if len(jitter) != B:
         raise ValueError(f"imageprep: {len(jitter)} jitter draws for {B} images")
-    order, factor = [-1] * (3 * B), [1.0] * (3 * B)
+    order, factor, shift = [-1] * (4 * B), [1.0] * (4 * B), [0] * B
     for b, j in enumerate(jitter):
         if j is None:
             continue
         ops, fs = j
-        if len(ops) != len(fs) or len(ops) > 3 or len(set(ops)) != len(ops) or any(o not in (0, 1, 2) for o in ops):
-            raise ValueError(f"imageprep: jitter of image {b} must be (order, factors) with each of 0, 1, 2 at most once, got {j!r}")
+        if len(ops) != len(fs) or len(ops) > 4 or len(set(ops)) != len(ops) or any(o not in (0, 1, 2, 3) for o in ops):
+            raise ValueError(f"imageprep: jitter of image {b} must be (order, factors) with each of 0, 1, 2, 3 at most once, got {j!r}")
         for k, (o, f) in enumerate(zip(ops, fs)):
-            if not (f >= 0):
+            if o == HUE:
+                shift[b] = hue_shift(f)
+            elif not (f >= 0):
                 raise ValueError(f"imageprep: jitter factor {f!r} of image {b} is negative")
-            order[3 * b + k], factor[3 * b + k] = int(o), float(np.float32(f))
-    return host_i32(order), (ctypes.c_float * (3 * B))(*factor)
+            order[4 * b + k], factor[4 * b + k] = int(o), float(np.float32(f))
+    return host_i32(order), (ctypes.c_float * (4 * B))(*factor), host_i32(shift)
 
 
 def _flags(flip, B):
@@ -239,7 +273,7 @@ def _pixels(imgs, windows, jitter, flip, dst_u8, dst_f32, normalizer, ori):
     B, (H, W, _) = len(imgs), imgs[0].shape
     dev = imgs[0].device
     windows, oh, ow = _windows(windows, B, H, W)
-    order, factor = _jitter_tables(jitter, B)
+    order, factor, shift = _jitter_tables(jitter, B)
     flags = _flags(flip, B)
     norm = None
     if normalizer is not None:
@@ -250,28 +284,30 @@ def _pixels(imgs, windows, jitter, flip, dst_u8, dst_f32, normalizer, ori):
         norm = (ctypes.c_float * 6)(*vals)
     pitch = W * 3
     base = [t.data_ptr() + ((windows[b][1] * W + windows[b][0]) * 3 if windows else 0) for b, t in enumerate(imgs)]
-    has_contrast = order is not None and any(order[k] == CONTRAST for k in range(3 * B))
+    has_contrast = order is not None and any(order[k] == CONTRAST for k in range(4 * B))
     sums = torch.empty(B, dtype=torch.int64, device=dev) if has_contrast else None
     for s, e in chunk_ranges(B, MAXB):
         tab = host_ptrs(base[s:e])
-        o = None if order is None else ctypes.addressof(order) + 12 * s
-        f = None if factor is None else ctypes.addressof(factor) + 12 * s
+        o = None if order is None else ctypes.addressof(order) + 16 * s
+        f = None if factor is None else ctypes.addressof(factor) + 16 * s
+        sh = None if shift is None else ctypes.addressof(shift) + 4 * s
         fl = None if flags is None else ctypes.addressof(flags) + 4 * s
         if has_contrast:
-            call("mopa_imageprep_contrast_sums", host_addr(tab), e - s, pitch, oh, ow, o, f, ptr(sums[s:e]), stream())
-        call("mopa_imageprep_pixels", host_addr(tab), e - s, pitch, oh, ow, o, f, None if sums is None else ptr(sums[s:e]), fl,
+            call("mopa_imageprep_contrast_sums4", host_addr(tab), e - s, pitch, oh, ow, o, f, sh, ptr(sums[s:e]), stream())
+        call("mopa_imageprep_pixels4", host_addr(tab), e - s, pitch, oh, ow, o, f, sh, None if sums is None else ptr(sums[s:e]), fl,
              None if dst_u8 is None else ptr(dst_u8[s:e]), None if dst_f32 is None else ptr(dst_f32[s:e]), host_addr(norm),
              None if ori is None else ptr(ori[s:e]), stream())
     return oh, ow
 
 
 def color_jitter_u8(images, jitter, windows=None) -> torch.Tensor:
-    """Brightness / contrast / saturation of ``ImageEnhance`` on B uint8 images: ``jitter[b]`` = ``(order, factors)`` as
-    ``draw_color_jitter`` returns it (operations 0 / 1 / 2 in the order they are applied, each at most once) or None.
-    Each operation is ``Image.blend(degenerate, image, factor)`` in float32: black for brightness, the grey image
-    ``L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16`` for saturation, the constant ``int(mean(L) + 0.5)`` of the image as it
-    stands in front of the contrast step for contrast (an exact integer reduction).  ``windows``: crop windows read through.
-    -> (B, h, w, 3) uint8."""
+    """Brightness / contrast / saturation of ``ImageEnhance`` and torchvision's ``adjust_hue`` on B uint8 images: ``jitter[b]`` =
+    ``(order, factors)`` as ``draw_color_jitter`` returns it (operations 0 / 1 / 2 / 3 in the order they are applied, each at
+    most once) or None.  The first three are ``Image.blend(degenerate, image, factor)`` in float32: black for brightness, the grey
+    image ``L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16`` for saturation, the constant ``int(mean(L) + 0.5)`` of the image
+    as it stands in front of the contrast step for contrast (an exact integer reduction).  Hue (factor in [-0.5, 0.5]) is Pillow's
+    RGB -> HSV, ``H = (H + hue_shift(factor)) & 255``, HSV -> RGB, made for a zero shift too (the round trip is lossy).
+    ``windows``: crop windows read through.  -> (B, h, w, 3) uint8."""
     imgs = _image_list(images)
     B, (H, W, _) = len(imgs), imgs[0].shape
     _, oh, ow = _windows(windows, B, H, W)

@@ -4,7 +4,9 @@ time around one call (host enqueue included), median of 50 after 5 warm-up calls
 achieved share of HBM bandwidth on the algorithmic bytes (raw image + mask + points in, img + ori_img + mask + indices out) against
 6.3 TB/s achievable.  Where Pillow and scipy are installed the host path of the same batch is timed too (one thread, the calls
 the datasets make per sample; refine_sam_mask restated with torch.unique + one compare per id); otherwise that row is left out.
-Writes a markdown table to stdout (and to argv[1] if given)."""
+``--hue`` puts a hue step (operation 3, between the first and the second blend) into every sample's jitter.
+Writes a markdown table to stdout (and to the file named on the command line, if one is)."""
+import argparse
 import statistics
 import sys
 import time
@@ -22,7 +24,7 @@ SHAPES = [("nuScenes 8 + 8, 1600x900 -> 400x225", 1600, 900, (400, 225), None, 3
 ORDERS = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
 
 
-def make(W, H, crop, n, B=16, seed=0):
+def make(W, H, crop, n, B=16, seed=0, hue=False):
     rng = np.random.Generator(np.random.PCG64(seed))
     out = []
     for b in range(B):
@@ -32,6 +34,9 @@ def make(W, H, crop, n, B=16, seed=0):
         pts = np.stack([rng.random(n) * (H * 0.6 - 1) + H * 0.4, rng.random(n) * (W - 1)], 1).astype(np.float32)
         s = {"image": img, "sam_mask": mask, "points_img": pts, "jitter": (ORDERS[b % 6], (0.8 + 0.03 * b, 1.3 - 0.02 * b, 1.1)),
              "flip": b % 2 == 1}
+        if hue:
+            order, fs = s["jitter"]
+            s["jitter"] = (order[:1] + (3,) + order[1:], fs[:1] + (0.1 - 0.0125 * b,) + fs[1:])
         if crop:
             left = int(rng.random() * (W + 1 - crop[0]))
             s["crop"] = (left, H - crop[1], left + crop[0], H)
@@ -64,6 +69,13 @@ def host_path(samples, resize):
             im = im.crop((l, t, r, b))
             m = m[t:b, l:r]
         for op, f in zip(*s["jitter"]):
+            if op == 3:                                           # torchvision's adjust_hue on a PIL image
+                hh, ss, vv = im.convert("HSV").split()
+                np_h = np.array(hh, dtype=np.uint8)
+                with np.errstate(over="ignore"):
+                    np_h += np.int32(f * 255).astype(np.uint8)
+                im = Image.merge("HSV", (Image.fromarray(np_h, "L"), ss, vv)).convert("RGB")
+                continue
             im = (ImageEnhance.Brightness, ImageEnhance.Contrast, ImageEnhance.Color)[op](im).enhance(f)
         x = np.array(im, dtype=np.float32) / 255.
         if s["flip"]:
@@ -74,9 +86,13 @@ def host_path(samples, resize):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", help="also write the table to this file")
+    ap.add_argument("--hue", action="store_true", help="a hue step in every sample's jitter")
+    args = ap.parse_args()
     lines = ["| batch | path | µs (median) | launches | algorithmic MB | GB/s | of 6.3 TB/s |", "|---|---|---|---|---|---|---|"]
     for name, W, H, resize, crop, n in SHAPES:
-        host = make(W, H, crop, n)
+        host = make(W, H, crop, n, hue=args.hue)
         samples = [{k: (torch.from_numpy(v).cuda() if isinstance(v, np.ndarray) else v) for k, v in s.items()} for s in host]
         w, h = resize or crop
         out = torch.empty(16, 3, h, w, device="cuda")
@@ -104,7 +120,7 @@ def main():
         us = statistics.median(ts)
         oh, ow = (H, W) if crop else (h, w)                       # ori_img: the uncropped image for SemanticKITTI
         byts = 16 * (H * W * 3 + H * W + n * 8 + h * w * 12 + oh * ow * 12 + h * w * 4 + 2 * n * 16)
-        lines.append(f"| {name} | prepare_batch | {us:,.1f} | {kernels} | {byts / 1e6:.1f} | {byts / us / 1e3:,.0f} | {byts / (us * 1e-6) / HBM:.3f} |")
+        lines.append(f"| {name} | prepare_batch{' with hue' if args.hue else ''} | {us:,.1f} | {kernels} | {byts / 1e6:.1f} | {byts / us / 1e3:,.0f} | {byts / (us * 1e-6) / HBM:.3f} |")
         try:
             import PIL  # noqa: F401
             import scipy  # noqa: F401
@@ -119,8 +135,8 @@ def main():
         lines.append(f"| {name} | host path (Pillow, scipy; one thread) | {statistics.median(hs):,.1f} | | | | |")
     text = "\n".join(lines)
     print(text)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if args.out:
+        with open(args.out, "w") as f:
             f.write(text + "\n")
 
 
