@@ -85,6 +85,12 @@ SECTIONS = [
  * mopa/data/semantic_kitti/semantic_kitti_dataloader.py:349-371,422-507 with select_points_in_frustum (:236-252); the pseudo-label
  * form (:430-469) takes the loaded keep mask instead of projecting.  Per-scan pointers and matrices are small host arrays (at most
  * 32 scans per call); the caller reads back the 2 B counts once, between mopa_kittiprep_count and mopa_kittiprep_scatter."""),
+    ("ground.hip", """Ground estimation on the device, all scans of an iteration per launch: the per-point ground mask that obj_on_road
+ * (mopa/data/mixmatch_ss.py:380-388) gets from Patchwork++ on the host and the shipped configs load from g_indices_dir
+ * (the preprocess.py of each dataset under mopa/data).  NOT the bits of Patchwork++: the published Patchwork core stated in DESIGN.md section 4 (504 patches
+ * in four concentric zones, per patch a plane fitted from the lowest points, uprightness / elevation / flatness tests), float64,
+ * deterministic; yardstick tests/_ground_reference.py.  The scans are the segments of one (sum N, cols) array, described by a small
+ * device table; no read-back."""),
     ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3).
  * Not in the reference (opt-in): mopa_grad_stats = per-parameter and total 2-norm, max |g| and non-finite count of the flat gradient
  * (what torch.nn.utils.clip_grad_norm_ and torch.isfinite would compute, without a host read), mopa_adam_flat_guarded = the same
