@@ -91,6 +91,15 @@ SECTIONS = [
  * in four concentric zones, per patch a plane fitted from the lowest points, uprightness / elevation / flatness tests), float64,
  * deterministic; yardstick tests/_ground_reference.py.  The scans are the segments of one (sum N, cols) array, described by a small
  * device table; no read-back."""),
+    ("objects.hip", """Object bank on the device, all scans and all requested classes of a call per launch: the instances that
+ * mopa/data/waymo/obj_point_extract.py:89-127 cuts out of labelled scans offline -- per (scan, class) the labels of
+ * sklearn.cluster.DBSCAN(eps=4, min_samples=5).fit_predict, exactly (uniform grid of side eps, core flags, lock-free union-find
+ * over core-core edges, clusters numbered by their lowest core point, border points to the lowest adjacent cluster), the float32
+ * range of every point, per instance (np.unique order: the noise group -1 first) the float64 mean range against max_distance,
+ * and the instances' points grouped in row order -- what the datasets' obj_sampling (mopa/data/nuscenes/nuscenes_dataloader.py:249-266,
+ * mopa/data/semantic_kitti/semantic_kitti_dataloader.py:404-419) later draws from.  Rows with a non-finite coordinate (sklearn raises
+ * on them) are left out and counted.  A fixed number of launches; the caller reads back the three counters once, to size its views;
+ * yardstick tests/_objects_reference.py."""),
     ("optim.hip", """Adam on one flat fp32 buffer == torch.optim.Adam as built by mopa/common/solver/build.py:7-21 (yaml BASE_LR 1e-3).
  * Not in the reference (opt-in): mopa_grad_stats = per-parameter and total 2-norm, max |g| and non-finite count of the flat gradient
  * (what torch.nn.utils.clip_grad_norm_ and torch.isfinite would compute, without a host read), mopa_adam_flat_guarded = the same
