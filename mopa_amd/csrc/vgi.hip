@@ -62,6 +62,63 @@ MOPA_API int mopa_vgi_first_points(const float* points, int32_t stride, int32_t 
   return MOPA_OK;
 }
 
+// ---------------------------------------------------------------- the same map for a voxel size that is no power of two
+// check_overlap (mixmatch_ss.py:215-331) picks a voxel's representative with sparse_quantize, which floors
+// `coords / np.array((vs,) * 3)` in FLOAT64, and then marks the grid at `floor(pc[idx] / voxel_size)`, a FLOAT32 quotient.  With a
+// power-of-two voxel size both quotients are exact and k_vgi_first is that rule.  Otherwise (the reference's default 0.2) they
+// differ for points near a voxel face, so: (a) rep[...] = first point of every float64 voxel, (b) a point that is its voxel's
+// representative marks the cell of its float32 floor.  |q32 - q64| <= 2^-23 |q| (two roundings of 2^-24 each), below 1 for every
+// cell a map can hold, so the two floors differ by at most one: `rep` is keyed by the float64 voxel over the map plus a margin
+// of one cell on every side and holds every representative that can mark a cell of the map.  No ground flags here: the
+// reference's ground lookup is not defined for these voxel sizes (mopa_amd/vgi.py::OverlapMap), `status` is cleared.
+__device__ __forceinline__ bool vgi_cell64(const float* __restrict__ p, double vs, int ox, int oy, int X, int Y, int zlo, int64_t* at) {
+  const double qx = floor(__ddiv_rn((double)p[0], vs)) - (double)(ox - 1), qy = floor(__ddiv_rn((double)p[1], vs)) - (double)(oy - 1);
+  const double qz = floor(__ddiv_rn((double)p[2], vs)) - (double)(zlo - 1);
+  if (!(qx >= 0.0 && qx < (double)(X + 2) && qy >= 0.0 && qy < (double)(Y + 2) && qz >= 0.0 && qz < (double)(VGI_ZR + 2))) return false;
+  *at = ((int64_t)qx * (Y + 2) + (int64_t)qy) * (VGI_ZR + 2) + (int64_t)qz;
+  return true;
+}
+__global__ void k_vgi_rep(const float* __restrict__ pts, int stride, int n, double vs, int ox, int oy, int X, int Y, int zlo,
+                          int* __restrict__ rep) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    int64_t at;
+    if (vgi_cell64(pts + (int64_t)i * stride, vs, ox, oy, X, Y, zlo, &at)) atomicMin(&rep[at], i);
+  }
+}
+__global__ void k_vgi_first_rep(const float* __restrict__ pts, int stride, int n, float vs, double vs64, int ox, int oy, int X, int Y,
+                                int zlo, const int* __restrict__ rep, int* __restrict__ first) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const float* p = pts + (int64_t)i * stride;
+    int64_t at;
+    if (!vgi_cell64(p, vs64, ox, oy, X, Y, zlo, &at) || rep[at] != i) continue;
+    const float fx = floorf(__fdiv_rn(p[0], vs)) - (float)ox, fy = floorf(__fdiv_rn(p[1], vs)) - (float)oy;
+    const float fz = floorf(__fdiv_rn(p[2], vs)) - (float)zlo;   // within one of the float64 cell: small integers, exact
+    if (!(fx >= 0.f && fx < (float)X && fy >= 0.f && fy < (float)Y && fz >= 0.f && fz < (float)VGI_ZR)) continue;
+    atomicMin(&first[((int64_t)fx * Y + (int64_t)fy) * VGI_ZR + (int64_t)fz], i);
+  }
+}
+MOPA_API size_t mopa_vgi_first_points_rep_workspace_bytes(int32_t X, int32_t Y) {
+  return align_up((size_t)(X + 2) * (Y + 2) * (VGI_ZR + 2) * sizeof(int), 256);
+}
+// first[...] = smallest index of the REPRESENTATIVES (first point of a float64 voxel of side voxel_size64) whose float32 floor
+// (p / voxel_size) is that cell, INT_MAX if none.
+MOPA_API int mopa_vgi_first_points_rep(const float* points, int32_t stride, int32_t n, float voxel_size, double voxel_size64, int32_t ox,
+                                       int32_t oy, int32_t X, int32_t Y, int32_t zlo, int32_t* first, int32_t* status, void* ws,
+                                       size_t ws_bytes, void* stream) {
+  if (n <= 0 || stride < 3 || X <= 0 || Y <= 0 || !(voxel_size > 0.f) || !(voxel_size64 > 0.0)) return MOPA_ERR_ARG;
+  if (ws_bytes < mopa_vgi_first_points_rep_workspace_bytes(X, Y)) return MOPA_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t cells = (int64_t)X * Y * VGI_ZR, rcells = (int64_t)(X + 2) * (Y + 2) * (VGI_ZR + 2);
+  int* rep = (int*)ws;
+  k_vgi_fill_i32<<<stream_grid(cells, 256), 256, 0, st>>>(first, cells, INT_MAX);
+  k_vgi_fill_i32<<<stream_grid(rcells, 256), 256, 0, st>>>(rep, rcells, INT_MAX);
+  if (hipMemsetAsync(status, 0, sizeof(int), st) != hipSuccess) return MOPA_ERR_LAUNCH;
+  k_vgi_rep<<<stream_grid(n, 256), 256, 0, st>>>(points, stride, n, voxel_size64, ox, oy, X, Y, zlo, rep);
+  k_vgi_first_rep<<<stream_grid(n, 256), 256, 0, st>>>(points, stride, n, voxel_size, voxel_size64, ox, oy, X, Y, zlo, rep, first);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
 // ---------------------------------------------------------------- overlap test: window OR of the occupancy, axis by axis
 // in: [X][Y][Zi] bytes (or, for the first pass, the `first` volume restricted to z slots [z0, z0 + Zi)); out[..][..][Zo],
 // out = OR over a window of `w` cells along the given axis.  Equivalent to the reference's dense conv3d with an all-ones
@@ -268,7 +325,7 @@ MOPA_API int mopa_vgi_road_height(const float* points, int32_t stride, int32_t n
                                   const uint8_t* g_mask, int32_t ox, int32_t oy, int32_t X, int32_t Y, int32_t zlo, int32_t cell_x,
                                   int32_t cell_y, double* out /*[2]*/, void* stream) {
   const int cx = cell_x - ox, cy = cell_y - oy;
-  if (n <= 0 || cx < 0 || cx >= X || cy < 0 || cy >= Y) return MOPA_ERR_ARG;
+  if (n <= 0 || stride < 3 || !(voxel_size > 0.f) || cx < 0 || cx >= X || cy < 0 || cy >= Y) return MOPA_ERR_ARG;
   k_vgi_road<<<1, 1024, 0, (hipStream_t)stream>>>(points, stride, n, voxel_size, first, g_mask, cx * Y + cy, zlo, cell_x, cell_y, out);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;

@@ -10,6 +10,7 @@ placement matrix.  Semantics and parity: ``oracle/vgi.py`` (fixture G8 = the ref
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -26,8 +27,32 @@ def _dev_f32(pc, device):
     return t.contiguous()
 
 
+def _is_pow2(v):
+    return math.frexp(v)[0] == 0.5
+
+
+def _voxel_reps(xyz, voxel_size):
+    """Rows of `xyz` that ``sparse_quantize`` keeps: the first point of every voxel of the FLOAT64 quotient."""
+    v = np.floor(xyz / np.array((voxel_size,) * 3)).astype(np.int32)
+    return np.sort(np.unique(v, axis=0, return_index=True)[1])
+
+
 class OverlapMap:
-    """Device state of one scan's search region: first-point volume, ground columns, and (per object) the free cells."""
+    """Device state of one scan's search region: first-point volume, ground columns, and (per object) the free cells.
+
+    Voxel sizes.  The reference takes a voxel's representative from ``sparse_quantize`` (a float64 quotient) and marks the grid at
+    the float32 floor of that representative (``oracle/vgi.py::overlap_grid``).  For a power-of-two ``voxel_size`` (the shipped
+    0.5) both quotients are exact and every point marks its voxel (``mopa_vgi_first_points``).  For any other one
+    (``check_overlap``'s default 0.2) the overlap test takes a second path that restates the two-step rule
+    (``mopa_vgi_first_points_rep``; the object's extents likewise come from its representatives) -- WITHOUT a ground mask only:
+    the reference's ground lookup compares ``new_center / voxel_size`` with voxel indices and takes the mean of an empty set
+    there (``mixmatch_ss.py:431-444``), so there is nothing to restate, and with ``g_mask`` the map is built as for a power of
+    two whatever the voxel size.
+
+    ``status`` (int32 (1,) on the device): bit 0 is set when a point with a ground flag fell inside the map in x / y but outside
+    its 128 z slots (z voxel below -64 or above 63), i.e. a ground voxel that ``ground2d`` / ``road_height`` cannot see.  It is 0
+    without a ground mask and when only non-ground points were dropped.  Nothing on the training path reads it (that would be
+    one more synchronisation); a caller may, e.g. ``int(m.status.item())`` when a placement looks wrong."""
 
     def __init__(self, pc_scan, voxel_size, search_range, z_min, front_axis, g_mask=None, device="cuda"):
         self.pts = _dev_f32(pc_scan, device)
@@ -54,13 +79,21 @@ class OverlapMap:
             self.g_mask = torch.as_tensor(np.asarray(g_mask).astype(np.uint8) if not torch.is_tensor(g_mask) else g_mask.to(torch.uint8)).to(dev).contiguous()
             if self.g_mask.numel() != self.pts.shape[0]:
                 raise RuntimeError("g_mask must hold one flag per scan point")
-        call("mopa_vgi_first_points", ptr(self.pts), self.pts.shape[1], self.pts.shape[0], float(np.float32(self.vs)), self.ox, self.oy,
-             self.X, self.Y, self.zlo, ptr(self.g_mask), ptr(self.first), ptr(self.status), stream())
+        self.by_reps = self.g_mask is None and not _is_pow2(self.vs)     # decided on the host: see the class docstring
+        if self.by_reps:
+            ws = workspace.get(query("mopa_vgi_first_points_rep_workspace_bytes", self.X, self.Y), dev)
+            call("mopa_vgi_first_points_rep", ptr(self.pts), self.pts.shape[1], self.pts.shape[0], float(np.float32(self.vs)), self.vs,
+                 self.ox, self.oy, self.X, self.Y, self.zlo, ptr(self.first), ptr(self.status), ptr(ws), ws.numel(), stream())
+        else:
+            call("mopa_vgi_first_points", ptr(self.pts), self.pts.shape[1], self.pts.shape[0], float(np.float32(self.vs)), self.ox, self.oy,
+                 self.X, self.Y, self.zlo, ptr(self.g_mask), ptr(self.first), ptr(self.status), stream())
         self._ground2d = None
 
     def free_cells(self, pc_obj, z_max=None):
         """The overlap test for one object -> dict(free (Xo,Yo,Zo) uint8 on the device or None, extent, offset, ori_range)."""
         obj = np.asarray(pc_obj)[:, :3]
+        if self.by_reps:                                  # the reference measures the object on its voxels' representatives
+            obj = obj[_voxel_reps(obj, self.vs)]
         ov = np.floor(obj / self.vs)                      # numpy keeps the object's dtype, like the reference
         zmax_v = self.zmin_v if z_max is None else z_max
         extent_z = np.max(ov, axis=0)[2] - np.min(ov, axis=0)[2] + 2
