@@ -5,7 +5,8 @@
 //   * forward conv (3x3 s1/s2, 1x1 s2, the 7x7 stem through a 16-wide tap trick),
 //   * backward-data (stride 1 directly; stride 2 as 4 output-parity classes so no FLOP is wasted on zeros),
 //   * ConvTranspose2d k2 s2 (4 output-parity classes of a 1x1 conv) and its backward-data (a 2x2 s2 conv),
-// selected by an index map, plus a split-K backward-weight kernel.
+// selected by an index map, plus a split-K backward-weight kernel.  The four parity classes of an operator go out as one launch
+// (k_conv2d_igemm_mfma_classes; ConvTranspose2d's weight gradient: k_convt_wgrad_mfma), with the bits of the per-class launches.
 //
 // Replaces the cuDNN calls behind mopa/models/resnet34_unet.py:93-110,144-182 (Conv2d / ConvTranspose2d of
 // UNetResNet34).  Oracle: oracle/net2d.py (torch-CPU conv2d / conv_transpose2d), golden fixture G1.
@@ -190,14 +191,11 @@ __global__ __launch_bounds__(256, 2) void k_conv2d_igemm(const float* __restrict
 // vector-FMA kernel above (A/B measurements in DESIGN.md).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// (the body of both kernels below; bx: the block's row tile)
 template <int BM, int BN, int WM, int WN, int KB>
-__global__ __launch_bounds__(256, 2) void k_conv2d_igemm_mfma(const float* __restrict__ in, const float* __restrict__ w,
-                                                               const float* __restrict__ bias, float* __restrict__ out,
-                                                               const ConvGeom g, int accumulate, int64_t bs_in, int64_t bs_w,
-                                                               int64_t bs_out) {
-  in += blockIdx.z * bs_in;
-  w += blockIdx.z * bs_w;
-  out += blockIdx.z * bs_out;
+__device__ __forceinline__ void igemm_mfma_block(const float* __restrict__ in, const float* __restrict__ w,
+                                                 const float* __restrict__ bias, float* __restrict__ out, const ConvGeom& g,
+                                                 const int accumulate, const int bx) {
   constexpr int MT = WM / 32, NT = WN / 32;
   static_assert((BM / WM) * (BN / WN) == 4 && WM % 32 == 0 && WN % 32 == 0, "four waves per block");
   constexpr int KQ = KB / 4;                  // k-quads per row: the 256 threads stage RPP = 256 / KQ rows per pass
@@ -210,7 +208,7 @@ __global__ __launch_bounds__(256, 2) void k_conv2d_igemm_mfma(const float* __res
   __shared__ int64_t rowoff[BM];             // output offset of each tile row (-1: beyond M)
   const int t = threadIdx.x;
   const int M = g.B * g.OHl * g.OWl;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+  const int m0 = bx * BM, n0 = blockIdx.y * BN;
   const int ohw = g.OHl * g.OWl;
   // staging assignment: A row = t/KQ + RPP*j, k-quad = t%KQ.  Per row: input coordinates and element offset at tap (0,0);
   // a tap adds a uniform delta, a K-chunk a uniform channel offset -> the loads of the loop are `uniform base + 32-bit
@@ -364,6 +362,37 @@ __global__ __launch_bounds__(256, 2) void k_conv2d_igemm_mfma(const float* __res
   }
 }
 
+template <int BM, int BN, int WM, int WN, int KB>
+__global__ __launch_bounds__(256, 2) void k_conv2d_igemm_mfma(const float* __restrict__ in, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, float* __restrict__ out,
+                                                               const ConvGeom g, int accumulate, int64_t bs_in, int64_t bs_w,
+                                                               int64_t bs_out) {
+  igemm_mfma_block<BM, BN, WM, WN, KB>(in + blockIdx.z * bs_in, w + blockIdx.z * bs_w, bias, out + blockIdx.z * bs_out, g, accumulate,
+                                       blockIdx.x);
+}
+
+// Four convolutions over one input and one output image in one launch: the output-parity classes of ConvTranspose2d(k2, s2)
+// and of the backward-data of a stride-2 convolution.  Each class keeps its own geometry (taps, logical grid, output offset) and
+// runs exactly the blocks of its own launch.  Blocks are dealt round-robin over the 8 XCDs (block i to XCD i % 8, each with its own
+// L2) and start in index order.  Classes of equal work (ConvTranspose2d): block 32 a + 8 class + j is row tile 8 a + j, so the
+// four classes of one row tile are consecutive blocks of ONE XCD, whose L2 serves the input tile to three of them.  Classes of
+// unequal work (stride-2 backward-data: 1, 2, 2 and 4 taps): class-major with the longest class first (the host orders them), row
+// tiles padded to a multiple of 8 per class, so every XCD gets an equal share of every class and the blocks that start last are the
+// short ones -- with the classes interleaved the 4-tap blocks of the last row tiles ran on alone: 0.83 x the per-class launches
+// at 16 images, against 1.3 x in this order.  Row tiles beyond a class's own count leave at once (before any barrier).
+struct ConvGeom4 { ConvGeom c[4]; };
+template <int BM, int BN, int WM, int WN, int KB>
+__global__ __launch_bounds__(256, 2) void k_conv2d_igemm_mfma_classes(const float* __restrict__ in, const float* __restrict__ w,
+                                                                       const float* __restrict__ bias, float* __restrict__ out,
+                                                                       const ConvGeom4 gs, int accumulate, int class_tiles) {
+  // class_tiles > 0 (classes of unequal work, the host has put the longest first): class-major, longest blocks first
+  const int cls = class_tiles ? blockIdx.x / class_tiles : (blockIdx.x >> 3) & 3;
+  const int bx = class_tiles ? (int)(blockIdx.x - cls * class_tiles) : (int)((blockIdx.x >> 5) << 3 | (blockIdx.x & 7));
+  const ConvGeom g = gs.c[cls];   // (a copy: a reference re-reads the kernel arguments inside the K loop)
+  if (bx * BM >= g.B * g.OHl * g.OWl) return;
+  igemm_mfma_block<BM, BN, WM, WN, KB>(in, w, bias, out, g, accumulate, bx);
+}
+
 // Tile choice, from measurements on MI355X at the network's own shapes (profiles/bench_igemm.py, B=8):
 //   M >= 200k pixels: 256x64 (8x8 register tile) 68-82 TF/s; with Cout % 128 == 0 and M >= 1M: 128x128 84 TF/s;
 //   M <  200k pixels (layer2-4, decoder stages 3-5): 64x64 (4x4 register tile) fills the 256 CUs -- 50-69 TF/s
@@ -422,6 +451,58 @@ static int igemm_launch(const float* in, const float* weight, const float* bias,
 MOPA_API int mopa_conv2d_igemm(const float* in, const float* weight, const float* bias, float* out,
                                const int32_t* geom_host, int32_t flags, void* stream) {
   return igemm_launch(in, weight, bias, out, geom_host, flags, 1, 0, 0, 0, stream);
+}
+
+// Four classes of one operator in one launch (k_conv2d_igemm_mfma_classes): geom4: 4 x 25 int32, one ConvGeom per class, over the same
+// images (B, IH, IW, OHa, OWa, Cin, Cout, ld_in, ld_out agree) and every class non-empty.  Each output element goes through the taps,
+// channel chunks and MFMA sequence of its class's own mopa_conv2d_igemm launch: same bits.  The tile is chosen from the rows of all
+// four classes.  flags as mopa_conv2d_igemm.  MFMA kernels only: MOPA_ERR_ARG where mopa_conv2d_igemm would take the vector pipe
+// (the caller keeps the four launches there).
+MOPA_API int mopa_conv2d_igemm_classes(const float* in, const float* weight, const float* bias, float* out,
+                                       const int32_t* geom4_host, int32_t flags, void* stream) {
+  ConvGeom4 gs;
+  memcpy(&gs, geom4_host, sizeof(gs));
+  const ConvGeom& g0 = gs.c[0];
+  if ((((uintptr_t)in | (uintptr_t)weight | (uintptr_t)out | (uintptr_t)bias) & 15) != 0) return MOPA_ERR_ARG;
+  int64_t Msum = 0, Mmax = 0;
+  for (int c = 0; c < 4; ++c) {
+    const ConvGeom& g = gs.c[c];
+    if (g.Cin % BK != 0 || g.Cout % 64 != 0 || g.ld_in % 4 != 0 || g.ld_out % 4 != 0 || g.B <= 0 || g.TH <= 0 || g.TW <= 0) return MOPA_ERR_ARG;
+    if (g.B != g0.B || g.IH != g0.IH || g.IW != g0.IW || g.OHa != g0.OHa || g.OWa != g0.OWa || g.Cin != g0.Cin || g.Cout != g0.Cout ||
+        g.ld_in != g0.ld_in || g.ld_out != g0.ld_out)
+      return MOPA_ERR_ARG;
+    const int64_t M = (int64_t)g.B * g.OHl * g.OWl;
+    if (g.OHl <= 0 || g.OWl <= 0 || M >= (1ll << 31)) return MOPA_ERR_ARG;
+    Msum += M;
+    if (M > Mmax) Mmax = M;
+  }
+  static const bool env_mfma = [] { const char* e = getenv("MOPA_CONV2D_MFMA"); return !e || atoi(e) != 0; }();
+  if (!env_mfma || (int64_t)g0.B * g0.IH * g0.IW * g0.ld_in >= (1ll << 30) || (int64_t)BK * g0.Cout >= (1ll << 28)) return MOPA_ERR_ARG;
+  const int tile = ((flags >> 8) & 0xff) ? ((flags >> 8) & 0xff) - 1 : pick_tile(Msum, g0.Cout, true);
+  if (tile < 0 || tile > 3 || tile == 1 || g0.Cout % kTiles[tile].bn) return MOPA_ERR_ARG;   // (128x128: never the MFMA choice)
+  const int64_t tiles8 = 8 * cdiv64(cdiv64(Mmax, kTiles[tile].bm), 8);   // (row tiles in groups of 8: see the kernel)
+  const int64_t gx = 4 * tiles8;
+  bool uneven = false;
+  for (int c = 1; c < 4; ++c) uneven |= gs.c[c].TH * gs.c[c].TW != g0.TH * g0.TW;
+  if (uneven)   // longest classes first (the classes are independent: their order is free)
+    for (int i = 1; i < 4; ++i)
+      for (int j = i; j > 0 && gs.c[j].TH * gs.c[j].TW > gs.c[j - 1].TH * gs.c[j - 1].TW; --j) {
+        const ConvGeom t = gs.c[j];
+        gs.c[j] = gs.c[j - 1];
+        gs.c[j - 1] = t;
+      }
+  const int class_tiles = uneven ? (int)tiles8 : 0;
+  if (gx >= (1ll << 31)) return MOPA_ERR_ARG;
+  dim3 grid((unsigned)gx, g0.Cout / kTiles[tile].bn);
+  hipStream_t st = (hipStream_t)stream;
+  const int accumulate = flags & 1;
+  switch (tile) {
+    case 0: k_conv2d_igemm_mfma_classes<256, 64, 64, 64, 16><<<grid, 256, 0, st>>>(in, weight, bias, out, gs, accumulate, class_tiles); break;
+    case 2: k_conv2d_igemm_mfma_classes<128, 64, 64, 32, 16><<<grid, 256, 0, st>>>(in, weight, bias, out, gs, accumulate, class_tiles); break;
+    default: k_conv2d_igemm_mfma_classes<64, 64, 32, 32, 16><<<grid, 256, 0, st>>>(in, weight, bias, out, gs, accumulate, class_tiles); break;
+  }
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
 }
 
 // nbatch independent convolutions of one geometry: problem z reads in + z*in_stride, weight + z*w_stride and writes
@@ -951,6 +1032,166 @@ MOPA_API int mopa_conv2d_bwd_weight(const float* in, const float* dy, float* dwe
   }
   const int64_t n = (int64_t)g.TH * g.TW * g.Cin * g.Cout;
   reduce_slabs2_launch(slabs, ns, n, dweight, accumulate, oihw, g.TH * g.TW, g.Cin, g.Cout, st);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Weight gradient of ConvTranspose2d(k2, s2): the four output-parity classes are four 1x1 problems over the SAME input pixels, so a
+// block of k_conv2d_wgrad_mfma<1, 1>'s shape (64 ci x 64 co over a slice of the pixels) stages its 16-pixel x tile once and
+// multiplies it with the dY tiles of the four classes (pixel (2 oy + ky, 2 ox + kx) of the output gradient).  Per class the pixel
+// slices, the staging and the MFMA sequence are those of the single-class launch: slab [split][ky * 2 + kx][Cin][Cout] holds the
+// same bits.  g: the geometry of class (0, 0).
+__global__ __launch_bounds__(256, 3) void k_convt_wgrad_mfma(const float* __restrict__ in, const float* __restrict__ dy,
+                                                           float* __restrict__ slabs, const ConvGeom g, int m_per_split) {
+  constexpr int WM = 64, WN = 64;
+  __shared__ __attribute__((aligned(16))) float As[2][WBK][WM + 4];
+  __shared__ __attribute__((aligned(16))) float Bs[2][4][WBK][WN + 4];
+  const int t = threadIdx.x;
+  const int tiles_n = g.Cout / WN;
+  const int ci0 = (blockIdx.y / tiles_n) * WM, co0 = (blockIdx.y % tiles_n) * WN;
+  const int M = g.B * g.IH * g.IW;
+  const int mbeg = blockIdx.z * m_per_split, mend = min(M, mbeg + m_per_split);
+  const int sk = t >> 4, sq = t & 15;   // staging: pixel k = t / 16, 4-float group = t % 16
+  const int lane = t & 63, wv = t >> 6;
+  const int wci = (wv & 1) * 32, wco = (wv >> 1) * 32;
+  const int l32 = lane & 31, lk = lane >> 5;
+  f32x16 acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[c][e] = 0.f;
+  float4 ra, rb[4];
+  bool ok;
+  int pb, poy, pox;
+  {
+    const int m = mbeg + sk;
+    pb = m / (g.IH * g.IW);
+    const int r = m - pb * g.IH * g.IW;
+    poy = r / g.IW;
+    pox = r - poy * g.IW;
+  }
+  const char* inb = reinterpret_cast<const char*>(in + ci0 + sq * 4);
+  const char* dyb = reinterpret_cast<const char*>(dy + co0 + sq * 4);
+  auto load_tile = [&](int mb) {
+    const int b = pb, oy = poy, ox = pox;
+    pox += WBK;
+    while (pox >= g.IW) {
+      pox -= g.IW;
+      if (++poy == g.IH) { poy = 0; ++pb; }
+    }
+    ok = mb + sk < mend;
+    const uint32_t off = ok ? (uint32_t)(((b * g.IH + oy) * g.IW + ox) * g.ld_in) * 4u : 0u;
+    ra = *reinterpret_cast<const float4*>(inb + off);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const uint32_t offb = ok ? (uint32_t)(((b * g.OHa + oy * 2 + (c >> 1)) * g.OWa + ox * 2 + (c & 1)) * g.ld_out) * 4u : 0u;
+      rb[c] = *reinterpret_cast<const float4*>(dyb + offb);
+    }
+  };
+  auto store_tile = [&](int buf) {   // (component-wise selects: see k_conv2d_wgrad_mfma)
+    *reinterpret_cast<float4*>(&As[buf][sk][sq * 4]) = make_float4(ok ? ra.x : 0.f, ok ? ra.y : 0.f, ok ? ra.z : 0.f, ok ? ra.w : 0.f);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      *reinterpret_cast<float4*>(&Bs[buf][c][sk][sq * 4]) =
+          make_float4(ok ? rb[c].x : 0.f, ok ? rb[c].y : 0.f, ok ? rb[c].z : 0.f, ok ? rb[c].w : 0.f);
+  };
+  int buf = 0;
+  if (mbeg < mend) {
+    load_tile(mbeg);
+    store_tile(0);
+  }
+  __syncthreads();
+  for (int mb = mbeg; mb < mend; mb += WBK) {
+    const bool more = mb + WBK < mend;
+    if (more) load_tile(mb + WBK);
+#pragma unroll
+    for (int kk = 0; kk < WBK; kk += 2) {
+      const float av = As[buf][kk + lk][wci + l32];
+      float bv[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) bv[c] = Bs[buf][c][kk + lk][wco + l32];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv[c], acc[c], 0, 0, 0);
+    }
+    if (more) {
+      store_tile(buf ^ 1);
+      __syncthreads();
+      buf ^= 1;
+    }
+  }
+  const int64_t wsz = (int64_t)4 * g.Cin * g.Cout;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    float* dst = slabs + (int64_t)blockIdx.z * wsz + ((int64_t)c * g.Cin + ci0 + wci) * g.Cout + co0 + wco + l32;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dst[(int64_t)(8 * (e >> 2) + 4 * lk + (e & 3)) * g.Cout] = acc[c][e];
+  }
+}
+
+// k_reduce_slabs2 for the slabs above, into ConvTranspose2d's parameter gradient [Cin][Cout][2][2]: dw (+)= the sum that the
+// single-class reduction (EW chosen from ONE class's Cin * Cout elements) left in the temporary, as the re-layout kernel added it.
+template <int EW>
+__global__ __launch_bounds__(256) void k_reduce_slabs_convt(const float* __restrict__ slabs, int nsplit, int64_t n, float* __restrict__ dw,
+                                                             int accumulate, int Cin, int Cout) {
+  constexpr int NL = 256 / EW;
+  __shared__ float red[NL][EW + 1];
+  const int el = threadIdx.x % EW, cl = threadIdx.x / EW;
+  const int64_t i = (int64_t)blockIdx.x * EW + el;
+  float s = 0.f;
+  if (i < n)
+#pragma unroll 8
+    for (int c = cl; c < nsplit; c += NL) s += slabs[(int64_t)c * n + i];
+  red[cl][el] = s;
+  __syncthreads();
+  if (cl == 0 && i < n) {   // i = (tap * Cin + ci) * Cout + co
+    const int co = (int)(i % Cout);
+    const int64_t r = i / Cout;
+    const int ci = (int)(r % Cin), tap = (int)(r / Cin);
+    const int64_t o = ((int64_t)ci * Cout + co) * 4 + tap;
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < NL; ++k) t += red[k][el];
+    dw[o] = (accumulate ? dw[o] : 0.f) + t;
+  }
+}
+
+// The single-class geometry (TH = TW = 1, KH0 = KW0 = 0) of class (0, 0) of a ConvTranspose2d(k2, s2) that the one-launch weight
+// gradient takes: x [B][IH][IW] -> dY [B][OHa >= 2 IH][OWa >= 2 IW].
+static bool convt_wgrad_geom(const ConvGeom& g) {
+  return g.B > 0 && g.IH > 0 && g.IW > 0 && g.OHl == g.IH && g.OWl == g.IW && g.OHa >= 2 * g.IH && g.OWa >= 2 * g.IW && g.OS == 2 &&
+         g.OOY == 0 && g.OOX == 0 && g.IS == 1 && g.IY0 == 0 && g.IX0 == 0 && g.TH == 1 && g.TW == 1 && g.Cin % 64 == 0 && g.Cin >= 64 &&
+         g.Cout % 64 == 0 && g.Cout >= 64 && g.ld_in % 4 == 0 && g.ld_out % 4 == 0 && g.ld_in >= g.Cin && g.ld_out >= g.Cout &&
+         (int64_t)g.B * g.IH * g.IW < (1ll << 31);
+}
+
+MOPA_API size_t mopa_convt_wgrad_workspace_bytes(const int32_t* geom_host) {
+  return 4 * mopa_conv2d_wgrad_workspace_bytes(geom_host);
+}
+
+// dweight [Cin][Cout][2][2] (the parameter's gradient tensor) (+)= the weight gradient of ConvTranspose2d(k2, s2) in one MFMA launch and
+// one slab reduction; geom: class (0, 0) as mopa_conv2d_bwd_weight takes it for a single class.  Same bits as four
+// mopa_conv2d_bwd_weight calls into a [2][2][Cin][Cout] temporary and mopa_conv2d_relayout_weight(mode 2, inverse).
+// flags: bit 0 = accumulate.  MFMA kernel only: MOPA_ERR_ARG where mopa_conv2d_bwd_weight would take the vector pipe.
+MOPA_API int mopa_convt_bwd_weight(const float* in, const float* dy, float* dweight, const int32_t* geom_host, int32_t flags, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  ConvGeom g;
+  memcpy(&g, geom_host, sizeof(g));
+  if (!convt_wgrad_geom(g) || !wgrad_use_mfma(g)) return MOPA_ERR_ARG;
+  if ((((uintptr_t)in | (uintptr_t)dy | (uintptr_t)ws) & 15) != 0) return MOPA_ERR_ARG;
+  if (ws_bytes < mopa_convt_wgrad_workspace_bytes(geom_host)) return MOPA_ERR_WORKSPACE;
+  int ns, mps;
+  wgrad_split(g, &ns, &mps);   // (of the single class: each tap's slabs and their summation order stay those of its own launch)
+  hipStream_t st = (hipStream_t)stream;
+  float* slabs = (float*)ws;
+  dim3 grid(1, (g.Cin / 64) * (g.Cout / 64), ns);
+  k_convt_wgrad_mfma<<<grid, 256, 0, st>>>(in, dy, slabs, g, mps);
+  const int64_t n1 = (int64_t)g.Cin * g.Cout, n = 4 * n1;
+  const int ew = reduce_ew(n1);
+  const unsigned nb = (unsigned)cdiv64(n, ew);
+  if (ew == 64) k_reduce_slabs_convt<64><<<nb, 256, 0, st>>>(slabs, ns, n, dweight, flags & 1, g.Cin, g.Cout);
+  else if (ew == 32) k_reduce_slabs_convt<32><<<nb, 256, 0, st>>>(slabs, ns, n, dweight, flags & 1, g.Cin, g.Cout);
+  else k_reduce_slabs_convt<16><<<nb, 256, 0, st>>>(slabs, ns, n, dweight, flags & 1, g.Cin, g.Cout);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }

@@ -70,6 +70,32 @@ def igemm(x_ptr, w, bias, out_ptr, geom, accumulate=False):
     call("mopa_conv2d_igemm", x_ptr, ptr(w), ptr(bias), out_ptr, ctypes.addressof(geom), int(accumulate), stream())
 
 
+# A/B switch (read at every call): the four output-parity classes of ConvTranspose2d(k2, s2) -- forward and weight gradient -- and of a
+# stride-2 convolution's backward-data run as ONE launch (mopa_conv2d_igemm_classes, mopa_convt_bwd_weight; same bits); 0: one launch
+# per class.  The one-launch kernels are MFMA only: the vector-pipe build keeps the per-class launches.
+CONV_CLASSES = os.environ.get("MOPA_CONV_CLASSES", "1") != "0"
+_CONV2D_MFMA = os.environ.get("MOPA_CONV2D_MFMA", "1") != "0"
+
+
+def conv_classes(x: "Img", out: "Img"):
+    """May the classes of an operator that reads x and writes (or, the weight gradient, reads) out go out as one launch?  (The MFMA
+    kernels address both images with 32-bit byte offsets.)"""
+    return CONV_CLASSES and _CONV2D_MFMA and x.rows * x.ld < (1 << 30) and out.rows * out.ld < (1 << 30)
+
+
+def igemm_classes(x_ptr, w, bias, out_ptr, geoms, accumulate=False):
+    """Four geometries over the same images in one launch."""
+    g4 = host_i32([v for g in geoms for v in g])
+    call("mopa_conv2d_igemm_classes", x_ptr, ptr(w), ptr(bias), out_ptr, ctypes.addressof(g4), int(accumulate), stream())
+
+
+def convt_wgrad(x_ptr, dy_ptr, dw, geom, dev, accumulate=False):
+    """ConvTranspose2d(k2, s2): dw is the parameter's gradient tensor [Cin][Cout][2][2]; geom: class (0, 0)."""
+    wsb = query("mopa_convt_wgrad_workspace_bytes", ctypes.addressof(geom))
+    ws = workspace.get(wsb, dev)
+    call("mopa_convt_bwd_weight", x_ptr, dy_ptr, ptr(dw), ctypes.addressof(geom), int(accumulate), ptr(ws), ws.numel(), stream())
+
+
 def igemm_batched(x_ptr, w_ptr, out_ptr, geom, nbatch, in_stride, w_stride, out_stride):
     """nbatch independent problems of one geometry in one launch (the 16 transform points of the Winograd path)."""
     call("mopa_conv2d_igemm_batched", x_ptr, w_ptr, out_ptr, ctypes.addressof(geom), nbatch, in_stride, w_stride, out_stride, 0,
@@ -578,8 +604,12 @@ class ConvOp:
             igemm(dout.p, wt, None, dx.p, g, acc_dx)
             return
         assert s == 2
-        if not acc_dx:
-            call("mopa_zero_rows", dx.p, dx.ld, dx.rows, dx.C, stream())   # (not a torch kernel: the pass may be a recorded command list)
+        self.dgrad_s2(x, dout, dx, wt, acc_dx)
+
+    def dgrad_s2(self, x: Img, dout: Img, dx: Img, wt, acc_dx: bool):
+        """Backward-data of the stride-2 convolution: the output-parity classes of dx, each with its own tap subset."""
+        k, p = self.k, self.p
+        geoms = []
         for ph in range(2):
             for pw in range(2):
                 khs = [kh for kh in range(k) if (ph + p - kh) % 2 == 0]
@@ -587,11 +617,18 @@ class ConvOp:
                 ohl, owl = (x.H - ph + 1) // 2, (x.W - pw + 1) // 2
                 if not khs or not kws or ohl <= 0 or owl <= 0:
                     continue
-                g = _geom(B=x.B, IH=dout.H, IW=dout.W, OHl=ohl, OWl=owl, OHa=x.H, OWa=x.W, OS=2, OOY=ph, OOX=pw,
-                          IY0=(ph + p - khs[0]) // 2, IX0=(pw + p - kws[0]) // 2, IDY=-1, IDX=-1, TH=len(khs),
-                          TW=len(kws), KH0=khs[0], KW0=kws[0], KS=2, KWF=k, Cin=self.O, Cout=self.I, ld_in=dout.ld,
-                          ld_out=dx.ld)
-                igemm(dout.p, wt, None, dx.p, g, True)
+                geoms.append(_geom(B=x.B, IH=dout.H, IW=dout.W, OHl=ohl, OWl=owl, OHa=x.H, OWa=x.W, OS=2, OOY=ph, OOX=pw,
+                                   IY0=(ph + p - khs[0]) // 2, IX0=(pw + p - kws[0]) // 2, IDY=-1, IDX=-1, TH=len(khs),
+                                   TW=len(kws), KH0=khs[0], KW0=kws[0], KS=2, KWF=k, Cin=self.O, Cout=self.I, ld_in=dout.ld,
+                                   ld_out=dx.ld))
+        if len(geoms) == 4 and conv_classes(dout, dx):
+            # four non-empty classes cover every pixel of dx once: the first writer writes (no zero pass, no read-add-write)
+            igemm_classes(dout.p, wt, None, dx.p, geoms, acc_dx)
+            return
+        if not acc_dx:
+            call("mopa_zero_rows", dx.p, dx.ld, dx.rows, dx.C, stream())   # (not a torch kernel: the pass may be a recorded command list)
+        for g in geoms:
+            igemm(dout.p, wt, None, dx.p, g, True)
 
 
 class ConvTOp:
@@ -607,20 +644,32 @@ class ConvTOp:
 
     def forward(self, x: Img, out: Img):
         wl = relayout_cached(self.w, (2, 2, self.I, self.O), self.O, self.I, 2, 2, 2)
+        geoms = [self._geom(x, out, ky, kx) for ky in range(2) for kx in range(2)]
+        if conv_classes(x, out):
+            igemm_classes(x.p, wl, self.b, out.p, geoms)
+            return
+        for g in geoms:
+            igemm(x.p, wl, self.b, out.p, g)
+
+    def wgrad(self, x: Img, dout: Img, dw, acc_params: bool = False):
+        """dw [Cin][Cout][2][2] (+)= the weight gradient: one MFMA launch and one slab reduction over the four classes, or one of each
+        per class into a temporary in the igemm layout and its re-layout."""
+        dev = self.w.device
+        if conv_classes(x, dout) and self.I % 64 == 0 and dout.H >= 2 * x.H and dout.W >= 2 * x.W:
+            convt_wgrad(x.p, dout.p, dw, self._geom(x, dout, 0, 0), dev, accumulate=acc_params)
+            return
+        dwl = torch.empty(2, 2, self.I, self.O, dtype=torch.float32, device=dev)
         for ky in range(2):
             for kx in range(2):
-                igemm(x.p, wl, self.b, out.p, self._geom(x, out, ky, kx))
+                g = self._geom(x, dout, ky, kx)
+                g[17], g[18] = 0, 0  # KH0/KW0: the per-class launch writes a single-tap slab
+                wgrad(x.p, dout.p, ptr(dwl, (ky * 2 + kx) * self.I * self.O), g, dev)
+        relayout(dwl, dw, self.O, self.I, 2, 2, 2, inverse=True, accumulate=acc_params)
 
     def backward(self, x: Img, dout: Img, dx: Img, dw, db, acc_params: bool = False, wgrad_side: bool = False, db_partial=None):
         dev = self.w.device
         with _on(wgrad_stream(dev) if wgrad_side else None, dout.t, db_partial):   # see ConvOp.backward
-            dwl = torch.empty(2, 2, self.I, self.O, dtype=torch.float32, device=dev)
-            for ky in range(2):
-                for kx in range(2):
-                    g = self._geom(x, dout, ky, kx)
-                    g[17], g[18] = 0, 0  # KH0/KW0: the per-class launch writes a single-tap slab
-                    wgrad(x.p, dout.p, ptr(dwl, (ky * 2 + kx) * self.I * self.O), g, dev)
-            relayout(dwl, dw, self.O, self.I, 2, 2, 2, inverse=True, accumulate=acc_params)
+            self.wgrad(x, dout, dw, acc_params)
             colsum(dout, db, accumulate=acc_params, partial=db_partial)
         wt = relayout_cached(self.w, (2, 2, self.O, self.I), self.O, self.I, 2, 2, 3)
         g = _geom(B=x.B, IH=dout.H, IW=dout.W, OHl=x.H, OWl=x.W, OHa=x.H, OWa=x.W, IS=2, TH=2, TW=2, KWF=2,
