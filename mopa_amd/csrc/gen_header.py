@@ -85,6 +85,15 @@ SECTIONS = [
  * mopa/data/semantic_kitti/semantic_kitti_dataloader.py:349-371,422-507 with select_points_in_frustum (:236-252); the pseudo-label
  * form (:430-469) takes the loaded keep mask instead of projecting.  Per-scan pointers and matrices are small host arrays (at most
  * 32 scans per call); the caller reads back the 2 B counts once, between mopa_kittiprep_count and mopa_kittiprep_scatter."""),
+    ("nuscprep.hip", """nuScenes' offline preprocessing of a sweep on the device, all sweeps of a call per launch: the float64 lidar -> ego ->
+ * global -> ego(cam) -> camera chain, the intrinsics, the perspective divide, the float32 cast and the strict frustum test of
+ * map_pointcloud_to_image (mopa/data/nuscenes/projection.py:9-90), the detection labels painted from the 3D boxes (the last
+ * labelled box that holds a point wins; mopa/data/nuscenes/preprocess.py:116-126 with the devkit's points_in_box), one ordered
+ * compaction (preprocess.py:111-114) and the ground mask of mopa/data/nuscenes/nuscenes_dataloader.py:305-316 (index lists go
+ * through mopa_kittiprep_ground).  Every matrix product is per element the fused chain fma(a[K-1], b[K-1], ... a0 * b0); rotation
+ * matrices, viewpad and the box frames are computed on the device (mopa_nuscprep_setup) from the quaternions, in a small table.
+ * Per-scan pointers are small host arrays (at most 32 scans per call, any number of boxes); the caller reads back the B counts
+ * once, between mopa_nuscprep_count and mopa_nuscprep_scatter."""),
     ("ground.hip", """Ground estimation on the device, all scans of an iteration per launch: the per-point ground mask that obj_on_road
  * (mopa/data/mixmatch_ss.py:380-388) gets from Patchwork++ on the host and the shipped configs load from g_indices_dir
  * (the preprocess.py of each dataset under mopa/data).  NOT the bits of Patchwork++: the published Patchwork core stated in DESIGN.md section 4 (504 patches
