@@ -606,8 +606,8 @@ class ConvOp:
         assert s == 2
         self.dgrad_s2(x, dout, dx, wt, acc_dx)
 
-    def dgrad_s2(self, x: Img, dout: Img, dx: Img, wt, acc_dx: bool):
-        """Backward-data of the stride-2 convolution: the output-parity classes of dx, each with its own tap subset."""
+    def dgrad_s2_geoms(self, x: Img, dout: Img, dx: Img):
+        """The non-empty output-parity classes of dx in a stride-2 convolution's backward-data, each with its own tap subset."""
         k, p = self.k, self.p
         geoms = []
         for ph in range(2):
@@ -621,6 +621,11 @@ class ConvOp:
                                    IY0=(ph + p - khs[0]) // 2, IX0=(pw + p - kws[0]) // 2, IDY=-1, IDX=-1, TH=len(khs),
                                    TW=len(kws), KH0=khs[0], KW0=kws[0], KS=2, KWF=k, Cin=self.O, Cout=self.I, ld_in=dout.ld,
                                    ld_out=dx.ld))
+        return geoms
+
+    def dgrad_s2(self, x: Img, dout: Img, dx: Img, wt, acc_dx: bool):
+        """Backward-data of the stride-2 convolution: one launch over its classes where all four exist, else one per class."""
+        geoms = self.dgrad_s2_geoms(x, dout, dx)
         if len(geoms) == 4 and conv_classes(dout, dx):
             # four non-empty classes cover every pixel of dx once: the first writer writes (no zero pass, no read-add-write)
             igemm_classes(dout.p, wt, None, dx.p, geoms, acc_dx)
