@@ -94,6 +94,15 @@ SECTIONS = [
  * matrices, viewpad and the box frames are computed on the device (mopa_nuscprep_setup) from the quaternions, in a small table.
  * Per-scan pointers are small host arrays (at most 32 scans per call, any number of boxes); the caller reads back the B counts
  * once, between mopa_nuscprep_count and mopa_nuscprep_scatter."""),
+    ("a2d2prep.hip", """A2D2's offline preprocessing of a frame on the device, all frames of a call per launch: undistort_image and
+ * DummyDataset.__getitem__ of mopa/data/a2d2/preprocess.py:26-44,96-141 -- cv2.undistort of the Telecam image and of the
+ * colour-coded label image as an inverse map built once per camera (float64, every operation rounded once; stored in OpenCV's
+ * CV_16SC2 + CV_16UC1 fixed-point layout, INTER_BITS = 5) and a bilinear remap with a constant 0 border (integer; the closed form
+ * of cv2.remap's 15-bit weight table), the label image read at every lidar point's [int32(row), int32(col)] (remapped on the
+ * spot, the same bytes as the full plane), the RGB code -> class index lookup of class_list.json (the last equal row wins, else
+ * K) and the float32 casts of points, reflectance / 255 and points_img.  The chain is stated in DESIGN.md section 4; yardstick
+ * tests/_a2d2_reference.py; OpenCV itself was not at hand.  Per-plane and per-frame pointers are small host arrays (at most 64
+ * planes, 32 frames per call); points outside the label image get K and are counted per frame on the device; no read-back."""),
     ("ground.hip", """Ground estimation on the device, all scans of an iteration per launch: the per-point ground mask that obj_on_road
  * (mopa/data/mixmatch_ss.py:380-388) gets from Patchwork++ on the host and the shipped configs load from g_indices_dir
  * (the preprocess.py of each dataset under mopa/data).  NOT the bits of Patchwork++: the published Patchwork core stated in DESIGN.md section 4 (504 patches
