@@ -8,6 +8,8 @@
 #define MOPA_ERR_ARG (-1)       // bad shape / unsupported channel count
 #define MOPA_ERR_WORKSPACE (-2) // workspace too small
 #define MOPA_ERR_LAUNCH (-3)    // hipGetLastError() != success after a launch
+#define MOPA_ERR_UNSUPPORTED (-4) // a JPEG stream outside the supported subset (jpeg_entropy.h): the caller falls back to another decoder
+#define MOPA_ERR_DATA (-5)      // a malformed JPEG stream
 
 #define MOPA_API extern "C" __attribute__((visibility("default")))
 

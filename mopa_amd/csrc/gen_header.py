@@ -103,6 +103,16 @@ SECTIONS = [
  * K) and the float32 casts of points, reflectance / 255 and points_img.  The chain is stated in DESIGN.md section 4; yardstick
  * tests/_a2d2_reference.py; OpenCV itself was not at hand.  Per-plane and per-frame pointers are small host arrays (at most 64
  * planes, 32 frames per call); points outside the label image get K and are counted per frame on the device; no read-back."""),
+    ("jpegdec.hip", """JPEG decoding split at the quantised coefficients -- np.asarray(Image.open(img_path)) in front of the 2D pipeline
+ * (mopa/data/nuscenes/nuscenes_dataloader.py:347-349), Pillow's bits.  Host half (csrc/jpeg_entropy.h, plain C++, no GPU needed):
+ * marker parser and Huffman decoding of baseline sequential streams (8-bit; 1 component, or 3 with chroma 1 x 1 and luma 1 x 1,
+ * 2 x 1 or 2 x 2; one interleaved scan; restart intervals; sides up to 8192) into int16 [blocks_y][blocks_x][64] planes in natural
+ * order behind the quantisation tables, and a JpegHeader (geometry, sampling, block counts, tables, plane offsets).  Everything else
+ * returns -4 (unsupported: the caller falls back to Pillow) before a coefficient is written, a malformed stream -5.  Device half,
+ * all images of a call in one launch (at most 32 images per call), a workgroup per tile of 14 x 2 MCUs: dequantisation + libjpeg's
+ * accurate integer inverse DCT ("islow") into uint8 component tiles in LDS, then libjpeg-turbo's "fancy" chroma upsampling, YCbCr ->
+ * RGB in 16-bit fixed point and the store into (H, W, 3) uint8 rows with a pitch; no workspace.  The chain is stated in DESIGN.md section 4; yardstick
+ * tests/_jpeg_reference.py, held against Pillow 12.2 (libjpeg-turbo) bit for bit."""),
     ("ground.hip", """Ground estimation on the device, all scans of an iteration per launch: the per-point ground mask that obj_on_road
  * (mopa/data/mixmatch_ss.py:380-388) gets from Patchwork++ on the host and the shipped configs load from g_indices_dir
  * (the preprocess.py of each dataset under mopa/data).  NOT the bits of Patchwork++: the published Patchwork core stated in DESIGN.md section 4 (504 patches
@@ -134,7 +144,8 @@ HEAD = """/* libmopa_hip.so -- C ABI of the MI355X-native MoPA hot path (gfx950 
  *   - every pointer is a DEVICE pointer unless its name ends in _host; `stream` is a hipStream_t;
  *   - plain pointers and sizes only (no torch types); no allocation, no global state, re-entrant per stream;
  *   - scratch memory is passed in (`ws`, `ws_bytes`); the matching *_workspace_bytes() query gives the size;
- *   - return value: 0 = ok, -1 = bad argument / unsupported shape, -2 = workspace too small, -3 = launch failed;
+ *   - return value: 0 = ok, -1 = bad argument / unsupported shape, -2 = workspace too small, -3 = launch failed,
+ *     -4 = JPEG stream outside the supported subset, -5 = malformed JPEG stream (jpegdec.hip only);
  *   - features are fp32 row-major [rows][ld] (ld >= C lets a layer address a channel slice of a wider buffer).
  * The reference has no FFI of its own (it is pure Python on torch + sparseconvnet); each group below names the
  * reference call sites whose arithmetic it replaces.  Binding example: INTEGRATION.md (ctypes), mopa_amd/_lib.py.
