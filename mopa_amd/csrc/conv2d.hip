@@ -1237,21 +1237,28 @@ MOPA_API int mopa_stem_bwd_weight_bn(const float* in, const float* dy, int32_t l
 #define SP 64
 #define SSLOTS 512   // float4 slots of one strip buffer (7 * (SP + 7) = 497 used)
 static_assert(7 * (SP + 7) <= SSLOTS && SP % 16 == 0, "strip staging: two float4 per thread");
-// One chunk's MFMAs of a wave with NT row tiles (rt0, rt0 + 2, ...): sp = the strip at (row rt0, this lane's float), bp = the staged
+// The PACKED rows: of a filter row's 32 floats only 7 pixels x 3 channels carry a weight (pixel 7 and channel 3 are zero in the image's
+// layout and in the weight's), so the kernel multiplies GEMM rows k = (ty * 7 + kw) * 3 + c of the 147 real taps, in 5 tiles of 32
+// (160 slots for 147) instead of 7: row k's operand is Ss[ty][4 * (pixel + kw) + c], one constant strip offset per lane and tile, and
+// its sums go to the slab position ty * 32 + 4 * kw + c they always had.  Rows 147..159 read the strip's first float and are not stored;
+// the slab's 77 padding rows are written as zeros.  Every stored element is the same fmaf chain over the same pixels: same bits.
+// Only where the slabs are summed into the parameter's [64][3][7][7] layout (k_reduce_slabs_stem drops the padding rows): in the
+// [7][2][16][64] layout they are results -- pixel 7 of a tap is a real pixel of the image -- and that layout keeps the 7 tiles.
+#define STEM_TAPS 147
+// One chunk's MFMAs of a wave with NT row tiles: sp = the strip at pixel lk, so[n] = this lane's row offset in tile n, bp = the staged
 // output gradient at (pixel lk, this lane's channel); pixel pair i is 8 floats / 2 rows further on.  The operands of pair i + 1 are
 // read from LDS before the MFMAs of pair i (the last pair reads itself again); np >= 1.
-template <int NT>
-__device__ __forceinline__ void stem_strip_mma(f32x16 (&acc)[4], const float* sp, const float* bp, int np) {
-  constexpr int SW = 4 * (SP + 7);
+template <int NT, int NA>
+__device__ __forceinline__ void stem_strip_mma(f32x16 (&acc)[NA], const float* sp, const int (&so)[NA], const float* bp, int np) {
   float b0 = bp[0], a0[NT];
 #pragma unroll
-  for (int n = 0; n < NT; ++n) a0[n] = sp[n * 2 * SW];
+  for (int n = 0; n < NT; ++n) a0[n] = sp[so[n]];
 #define STEM_STRIP_PAIR(I)                                                                                          \
   {                                                                                                                 \
     const int nx = min((I) + 1, np - 1);                                                                            \
     const float b1 = bp[nx * 128];                                                                                  \
     float a1[NT];                                                                                                   \
-    _Pragma("unroll") for (int n = 0; n < NT; ++n) a1[n] = sp[n * 2 * SW + nx * 8];                                 \
+    _Pragma("unroll") for (int n = 0; n < NT; ++n) a1[n] = sp[so[n] + nx * 8];                                      \
     _Pragma("unroll") for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[n], b0, acc[n], 0, 0, 0); \
     b0 = b1;                                                                                                        \
     _Pragma("unroll") for (int n = 0; n < NT; ++n) a0[n] = a1[n];                                                   \
@@ -1264,7 +1271,7 @@ __device__ __forceinline__ void stem_strip_mma(f32x16 (&acc)[4], const float* sp
   for (; i < np; ++i) STEM_STRIP_PAIR(i)
 #undef STEM_STRIP_PAIR
 }
-template <bool BNB>
+template <bool BNB, bool PACKED>
 __global__ __launch_bounds__(256, 2) void k_stem_wgrad_strip(const float* __restrict__ in, const float* __restrict__ dy,
                                                               float* __restrict__ slabs, const ConvGeom g, int m_per_split,
                                                               const StemBn bn) {
@@ -1283,14 +1290,23 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_strip(const float* __rest
   const int M = g.B * g.OHl * g.OWl, ohw = g.OHl * g.OWl;
   const int mbeg = blockIdx.x * m_per_split, mend = min(M, mbeg + m_per_split);
   const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);   // (the wave's row tiles are a scalar branch, not an exec mask)
-  const int wco = (wv & 1) * 32, rt0 = wv >> 1;
+  // A wave takes row tiles of one channel half, which share its dY operand.  PACKED: 5 tiles x 2 halves over 4 waves, tiles 0, 1, 2
+  // (wave pair 0) or 3, 4 (pair 1); else 7 tiles, 0, 2, 4, 6 or 1, 3, 5.  (Swapping the pairs in every other block -- by bit 0, 3, 5, 8
+  // or 9 of the block index -- so that a SIMD's resident waves carry 3 + 2 tiles changed nothing: profiles/r28_stem_packed.md.)
+  constexpr int NA = PACKED ? 3 : 4;
+  const int wp = wv >> 1;
+  const int wco = (wv & 1) * 32;
   const int l32 = lane & 31, lk = lane >> 5;
   const int ld_dy = BNB ? bn.ld_dy : g.ld_out;
-  f32x16 acc[4];
+  f32x16 acc[NA];
+  int so[NA];   // this lane's GEMM row of tile n, as a strip offset
 #pragma unroll
-  for (int n = 0; n < 4; ++n)
+  for (int n = 0; n < NA; ++n) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
+    const int k = (wp * 3 + n) * 32 + l32;
+    so[n] = !PACKED ? (wp + 2 * n) * SW + l32 : k < STEM_TAPS ? (k / 21) * SW + 4 * ((k % 21) / 3) + k % 3 : 0;
+  }
   // staging: strip slot e = t + 256 j = (row e / (SP + 7), pixel column e % (SP + 7)); output gradient: pixel t / 16 + 16 j, quad t % 16
   int scol[2], soff[2];
 #pragma unroll
@@ -1369,11 +1385,11 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_strip(const float* __rest
   while (len > 0) {
     const bool more = cm < mend;
     if (more) load_chunk();
-    const float* sp = &Ss[buf][rt0 * SW + 4 * lk + l32];
+    const float* sp = &Ss[buf][4 * lk];
     const float* bp = &Bs[buf][lk][wco + l32];
     const int np = (len + 1) >> 1;   // pixel pairs (an odd chunk's last slot is zero)
-    if (rt0 == 0) stem_strip_mma<4>(acc, sp, bp, np);   // row tiles 0, 2, 4, 6
-    else stem_strip_mma<3>(acc, sp, bp, np);            // row tiles 1, 3, 5
+    if (wp == 0) stem_strip_mma<NA, NA>(acc, sp, so, bp, np);
+    else stem_strip_mma<NA - 1, NA>(acc, sp, so, bp, np);
     if (more) {
       store_chunk(buf ^ 1);
       __syncthreads();
@@ -1383,13 +1399,24 @@ __global__ __launch_bounds__(256, 2) void k_stem_wgrad_strip(const float* __rest
       len = 0;
     }
   }
-  float* dst = slabs + (int64_t)blockIdx.x * STEM_ROWS * 64 + wco + l32;
+  float* slab = slabs + (int64_t)blockIdx.x * STEM_ROWS * 64;
+  float* dst = slab + wco + l32;
 #pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const int rt = rt0 + 2 * n;
-    if (rt < 7) {
+  for (int n = 0; n < NA; ++n) {
+    const int rt = PACKED ? wp * 3 + n : wp + 2 * n;
+    if (rt < (PACKED ? 5 : 7)) {
 #pragma unroll
-      for (int e = 0; e < 16; ++e) dst[(int64_t)(rt * 32 + 8 * (e >> 2) + 4 * lk + (e & 3)) * 64] = acc[n][e];
+      for (int e = 0; e < 16; ++e) {
+        const int k = rt * 32 + 8 * (e >> 2) + 4 * lk + (e & 3);
+        if (!PACKED) dst[k * 64] = acc[n][e];
+        else if (k < STEM_TAPS) dst[((k / 21) * 32 + 4 * ((k % 21) / 3) + k % 3) * 64] = acc[n][e];
+      }
+    }
+  }
+  if (PACKED) {   // the slab's padding rows (channel 3 of pixels 0..6 and pixel 7 of every filter row): the reduction reads every row
+    for (int i = t; i < (STEM_ROWS - STEM_TAPS) * 64; i += 256) {
+      const int p = i >> 6, q = p % 11;
+      slab[((p / 11) * 32 + (q < 7 ? 4 * q + 3 : q + 21)) * 64 + (i & 63)] = 0.f;
     }
   }
 }
@@ -1439,8 +1466,11 @@ static int stem_wgrad2_launch(const float* in, const float* dy, float* dweight, 
   wgrad_split(g, &ns, &mps);
   hipStream_t st = (hipStream_t)stream;
   float* slabs = (float*)ws;
-  if (bn) k_stem_wgrad_strip<true><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, *bn);
-  else k_stem_wgrad_strip<false><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, StemBn{});
+  // the packed row tiles where the padding rows are dropped anyway (k_reduce_slabs_stem); the [7][2][16][64] layout holds them as results
+  if (bn && param) k_stem_wgrad_strip<true, true><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, *bn);
+  else if (bn) k_stem_wgrad_strip<true, false><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, *bn);
+  else if (param) k_stem_wgrad_strip<false, true><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, StemBn{});
+  else k_stem_wgrad_strip<false, false><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, StemBn{});
   const int n = STEM_ROWS * 64;
   if (param) k_reduce_slabs_stem<<<n / 16, 256, 0, st>>>(slabs, ns, dweight, accumulate);
   else reduce_slabs2_launch(slabs, ns, n, dweight, accumulate, 0, 14, 16, 64, st);
@@ -1465,6 +1495,161 @@ MOPA_API int mopa_stem_bwd_weight_bn2(const float* in, const float* dy, int32_t 
     return MOPA_ERR_ARG;
   const StemBn bn{xbn, stats, coef, ld_x, ld_dy, g.B / n_groups, n_groups, training};
   return stem_wgrad2_launch(in, dy, dweight, geom_host, flags, ws, ws_bytes, stream, &bn);
+}
+
+// The stem's FORWARD from the same image strip, over the packed taps.  A chunk is a run of up to FSP output pixels of one output
+// row, one 32-pixel tile per wave; the block stages its 7 rows x (FSP + 7) pixels CHANNEL-PLANAR (Fs[ty][c][column]: the lanes of an
+// MFMA's A operand are 32 consecutive pixels, one float apart) and keeps the packed weight Wf[k][64], k = (ty * 7 + kw) * 3 + c, in
+// LDS for all its chunks.  Every output element is the fmaf chain of mopa_conv2d_igemm on the stem geometry (filter row, 4-pixel tap,
+// slot: k ascending) without the terms whose weight is zero, which leave an accumulator that started at +0 as it is: same bits.
+// K = 148: the 147 taps and one zero row, since an MFMA takes two; the odd lanes' operand of that row is the strip's (6, 0, pixel + 7).
+// The next chunk's loads are issued before the current chunk's MFMAs, the output stores go out behind them and complete under the
+// next chunk's (one barrier per chunk: the staging stores go to the other buffer).
+#define FSP 128
+#define FCW (FSP + 7)
+#define FKP 74   // MFMA k pairs
+static_assert(2 * FKP > STEM_TAPS && 2 * FKP - STEM_TAPS == 1, "one zero row");
+__host__ __device__ constexpr int stem_fwd_off(int k) { return ((k / 21) * 3 + k % 3) * FCW + (k % 21) / 3; }
+__global__ __launch_bounds__(256, 2) void k_stem_fwd_strip(const float* __restrict__ in, const float* __restrict__ w,
+                                                            float* __restrict__ out, const ConvGeom g, int chunks_per_block, int nchunks) {
+  constexpr int NS = (7 * FCW + 255) / 256;   // strip float4 per thread and chunk
+  __shared__ __attribute__((aligned(16))) float Wf[2 * FKP][64];
+  __shared__ float Fs[2][21 * FCW];
+  const int t = threadIdx.x;
+  for (int i = t; i < 2 * FKP * 16; i += 256) {   // the [7][2][16][64] weight, real slots only
+    const int k = i >> 4, q = i & 15;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (k < STEM_TAPS) v = *reinterpret_cast<const float4*>(w + ((k / 21) * 32 + 4 * ((k % 21) / 3) + k % 3) * 64 + q * 4);
+    *reinterpret_cast<float4*>(&Wf[k][q * 4]) = v;
+  }
+  const int lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int l32 = lane & 31, lk = lane >> 5;
+  // staging: strip slot e = t + 256 j = (row e / FCW, pixel column e % FCW)
+  int scol[NS], soff[NS], sdst[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int e = t + 256 * j, r = e / FCW, col = e - r * FCW;
+    scol[j] = e < 7 * FCW ? col : 2 * FSP;   // (a slot past the strip is never inside a chunk and is not stored)
+    soff[j] = (r * g.IW + col) * 4;
+    sdst[j] = r * 3 * FCW + col;
+  }
+  float4 rs[NS];
+  // the chunk cursor: block-uniform
+  const int cpr = (g.OWl + FSP - 1) / FSP;   // chunks per output row
+  int cc = blockIdx.x * chunks_per_block;
+  const int cend = min(nchunks, cc + chunks_per_block);
+  int crow = __builtin_amdgcn_readfirstlane(cc / cpr), cxc = cc - crow * cpr;   // crow = image * OHl + output row
+  int cb = __builtin_amdgcn_readfirstlane(crow / g.OHl), cy = crow - cb * g.OHl;
+  int llen = 0;
+  int64_t lout = 0;   // length and first output element of the chunk in the registers
+  auto load_chunk = [&]() {
+    const int cx = cxc * FSP;
+    const int len = min(FSP, g.OWl - cx);
+    const float* sbase = in + ((int64_t)(cb * g.IH + cy) * g.IW + cx) * 4;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) rs[j] = *reinterpret_cast<const float4*>(sbase + (scol[j] < len + 7 ? soff[j] : 0));
+    llen = len;
+    lout = ((int64_t)(cb * g.OHa + cy) * g.OWa + cx) * g.ld_out;
+    ++cc;
+    if (++cxc == cpr) {
+      cxc = 0;
+      if (++cy == g.OHl) { cy = 0; ++cb; }
+    }
+  };
+  auto store_chunk = [&](int buf) {   // (columns past the chunk hold the chunk's first pixel: finite, and no output reads them)
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      if (scol[j] < FCW) {
+        float* d = &Fs[buf][sdst[j]];
+        d[0] = rs[j].x;
+        d[FCW] = rs[j].y;
+        d[2 * FCW] = rs[j].z;
+      }
+    }
+  };
+  int buf = 0, len = 0;
+  int64_t obase = 0;
+  if (cc < cend) {
+    load_chunk();
+    store_chunk(0);
+    len = llen;
+    obase = lout;
+  }
+  __syncthreads();
+  const int p0 = wv * 32;
+  // the odd lanes' operand is 1 channel plane, 1 pixel less 2 planes, or 1 filter row less 6 pixels behind the even lanes'
+  const int d1 = lk * FCW, d2 = lk * (1 - 2 * FCW), d3 = lk * (FCW - 6);
+  while (len > 0) {
+    const bool more = cc < cend;
+    if (more) load_chunk();
+    if (p0 < len) {
+      f32x16 acc[2];
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
+      const float* sp = &Fs[buf][p0 + l32];
+      const float* sp1 = sp + d1;
+      const float* sp2 = sp + d2;
+      const float* sp3 = sp + d3;
+      const float* bp = &Wf[lk][l32];
+      static_assert(stem_fwd_off(STEM_TAPS - 1) + 1 - 2 * FCW == 18 * FCW + 7, "the zero row's operand");
+      // pair j's operands: constant LDS offsets from one of three per-lane bases; read one pair ahead of the MFMAs
+#define STEM_FWD_A(J)                                                                                               \
+  ((2 * (J) + 1 >= STEM_TAPS || stem_fwd_off(2 * (J) + 1) - stem_fwd_off(2 * (J)) == 1 - 2 * FCW ? sp2              \
+    : stem_fwd_off(2 * (J) + 1) - stem_fwd_off(2 * (J)) == FCW                                   ? sp1              \
+                                                                                                  : sp3)[stem_fwd_off(2 * (J))])
+      float a0 = STEM_FWD_A(0), b00 = bp[0], b01 = bp[32];
+#pragma unroll
+      for (int j = 0; j < FKP; ++j) {
+        const int nx = j + 1 < FKP ? j + 1 : j;   // (the last pair reads itself again)
+        const float a1 = STEM_FWD_A(nx), b10 = bp[nx * 128], b11 = bp[nx * 128 + 32];
+        __builtin_amdgcn_sched_barrier(0);   // (unrolled, the scheduler sinks each read to its use and waits for it there)
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b00, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b01, acc[1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        a0 = a1;
+        b00 = b10;
+        b01 = b11;
+      }
+#undef STEM_FWD_A
+      float* o = out + obase + l32;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int p = p0 + 8 * (e >> 2) + 4 * lk + (e & 3);
+        if (p < len) {
+          o[p * g.ld_out] = acc[0][e];
+          o[p * g.ld_out + 32] = acc[1][e];
+        }
+      }
+    }
+    if (more) {
+      store_chunk(buf ^ 1);
+      __syncthreads();
+      buf ^= 1;
+      len = llen;
+      obase = lout;
+    } else {
+      len = 0;
+    }
+  }
+}
+// out[m][0..63] (row stride ld_out) = the stem convolution of the NHWC4 image `in` with `weight` in mopa_conv2d_stem_relayout's
+// [7][2][16][64] form: mopa_conv2d_igemm's bits on the dense stem geometry (stem_strip_geom with the whole filter as taps; anything
+// else is MOPA_ERR_ARG: mopa_conv2d_igemm takes it).  No bias, no accumulation.
+MOPA_API int mopa_stem_fwd(const float* in, const float* weight, float* out, const int32_t* geom_host, void* stream) {
+  ConvGeom g;
+  memcpy(&g, geom_host, sizeof(g));
+  if (!stem_strip_geom(g) || g.KS != 1 || g.KH0 != 0 || g.KW0 != 0 || g.KWF != 2 || g.ld_out < 64 || !in || !weight || !out)
+    return MOPA_ERR_ARG;
+  if ((((uintptr_t)in | (uintptr_t)weight) & 15) != 0 || ((uintptr_t)out & 3) != 0) return MOPA_ERR_ARG;
+  if ((int64_t)FSP * g.ld_out >= (1ll << 31)) return MOPA_ERR_ARG;
+  const int64_t nchunks = (int64_t)g.B * g.OHl * ((g.OWl + FSP - 1) / FSP);
+  if (nchunks >= (1ll << 31)) return MOPA_ERR_ARG;
+  const int64_t cpb = cdiv64(nchunks, 1024);   // (at most 1,024 blocks: the packed weight is staged once per block)
+  k_stem_fwd_strip<<<(unsigned)cdiv64(nchunks, cpb), 256, 0, (hipStream_t)stream>>>(in, weight, out, g, (int)cpb, (int)nchunks);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -705,6 +705,17 @@ STEM_BN_FUSED_BWD = os.environ.get("MOPA_STEM_BN_FUSED_BWD", "1") != "0" and os.
 STEM_BWD2 = frozenset({"1": ("wgrad", "pool"), "0": ()}.get(os.environ.get("MOPA_STEM_BWD2", "1"), (os.environ.get("MOPA_STEM_BWD2"),)))
 # (stem pixels B * Hp * Wp from which the second form runs: one 302 x 480 image is inside; profiles/r12_stem_bwd.md)
 STEM_BWD2_MIN_PIXELS = int(os.environ.get("MOPA_STEM_BWD2_MIN_PIXELS", str(1 << 17)))
+# A/B switch (read at every call): the stem's forward over its 147 real taps from an image strip in LDS (mopa_stem_fwd) instead of the
+# implicit GEMM over 7 x 32 padded slots; 0 = mopa_conv2d_igemm.  Same bits (profiles/r28_stem_packed.md).  An MFMA kernel.
+STEM_PACKED = os.environ.get("MOPA_STEM_PACKED", "1") != "0"
+
+
+def stem_forward(x_ptr, w, out_ptr, geom):
+    """The stem convolution on its dense geometry (NHWC4 image, [7][2][16][64] weight, no bias)."""
+    if STEM_PACKED and _CONV2D_MFMA and geom[0] * geom[1] * geom[2] < 1 << 29:   # (csrc/conv2d.hip::stem_strip_geom's image limit)
+        call("mopa_stem_fwd", x_ptr, ptr(w), out_ptr, ctypes.addressof(geom), stream())
+    else:
+        igemm(x_ptr, w, None, out_ptr, geom)
 # A/B switch: the residual BatchNorms (bn2 of every BasicBlock) leave one bit per element, pre-activation > 0, and their backward pass
 # reads that bit instead of the whole saved output (mopa_bn_act_fwd_groups_bits / mopa_bn_act_bwd_groups_fused)
 BN_MASK_BITS = os.environ.get("MOPA_BN_MASK_BITS", "1") != "0"
@@ -954,7 +965,7 @@ def _backbone_forward(P, imgc, training, drop_p, drop_seed, seed_t, dev, groups=
     c1 = Img(J[0], B, Hp, Wp, 0, 64) if lazy_stem else new_img(B, Hp, Wp, 64, dev)
     stem_g = _geom(B=B, IH=Hp + 6, IW=Wp + 8, OHl=Hp, OWl=Wp, OHa=Hp, OWa=Wp, IDX=4, TH=7, TW=2, KWF=2, Cin=16,
                    Cout=64, ld_in=4, ld_out=c1.ld)
-    igemm(ptr(x4), w1, None, c1.p, stem_g)
+    stem_forward(ptr(x4), w1, c1.p, stem_g)
     bn1 = BnOp(P, pre + "bn1", G=G, stem_grid=(B, Hp, Wp))   # (the stem's and the max-pool's backward ask this layer's plan)
     tape.append(("stem", x4, c1, stem_g, bn1))
     H2, W2 = Hp // 2, Wp // 2
