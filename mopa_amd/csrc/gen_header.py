@@ -71,6 +71,16 @@ SECTIONS = [
  * the image-index transforms of Dataset.__getitem__ (mopa/data/nuscenes/nuscenes_dataloader.py:347-408,
  * mopa/data/semantic_kitti/semantic_kitti_dataloader.py:563-630, mopa/data/utils/refine_pseudo_labels.py:72-102); bit-exact.
  * Per-image pointers and draws are small host arrays (at most 32 images per call); one launch per stage for the whole batch."""),
+    ("denselabels.hip", """Dense 2D pseudo labels from SAM masks on the device, all samples of a call per launch: refine_sam_2Dlabels
+ * (mopa/data/utils/refine_pseudo_labels.py:25-69) behind the row expansion of SemanticKITTISCN.preprocess
+ * (mopa/data/semantic_kitti/semantic_kitti_dataloader.py:443-451) and the crop + flip of __getitem__ (:587-590,:611-613): maximum
+ * and first arg-max of the never-built (N, C) rows, the per-class median refinement (mopa_refine_pseudo_labels_segmented, one segment
+ * per image), the scatter in which the last point of a pixel wins, per mask id the pixel count and the class sums of the winning
+ * rows (int64 fixed point, 2^-40 units, integer atomics: the same bits on every run), the fill of every id below the area
+ * threshold with its first arg-max, and the crop window and flip in the store.  Equal to the reference wherever the float64 sums
+ * decide an id (DESIGN.md section 4); points outside the image, with a raw label >= C or a probability outside [0, 1] are skipped
+ * and counted per image on the device.  Per-image pointers and draws are small host arrays (at most 32 images per call); the same
+ * number of launches for every batch size; no read-back."""),
     ("scanprep.hip", """The 3D half of the input pipeline on the device, all scans of an iteration per launch: rotation, voxel coordinates
  * and in-field filter of augment_and_scale_3d + Dataset.__getitem__ (mopa/data/utils/augmentation_3d.py:48-59,
  * mopa/data/nuscenes/nuscenes_dataloader.py:339-340,410-465, mopa/data/semantic_kitti/semantic_kitti_dataloader.py:583-585,632-676),

@@ -15,6 +15,9 @@ per sample on the host in ``__getitem__`` (``mopa/data/nuscenes/nuscenes_dataloa
 4. ``prepare_sam_mask``    ``scipy.ndimage.zoom(mask, 0.25, order=0)`` + ``refine_sam_mask`` (``refine_pseudo_labels.py:72-102``) + crop + flip.
 5. ``prepare_img_indices`` the transforms of ``points_img`` (scale with floor, crop origin, ``astype(int64)``, flip).
 
+``prepare_dense_pslabels`` (``csrc/denselabels.hip``, fixture G17) is SemanticKITTI's ``refine_sam_2Dlabels`` for samples with loaded 2D pseudo
+labels: ``full_2d_pslabels``, equal to the reference wherever the summed rows decide a mask id.
+
 ``prepare_batch`` runs the five stages for the B samples of an iteration with one launch per stage.  The random decisions stay
 with the caller (``draw_color_jitter``, ``draw_flip``, ``draw_bottom_crop`` draw them in the reference's order from the reference's
 generators); the device part is deterministic.  There is no CPU fallback and -- in the resize form -- no host synchronisation;
@@ -397,6 +400,82 @@ def prepare_sam_mask(masks, size=None, max_h=None, row_min=None, max_area_thre=0
     return out
 
 
+# ------------------------------------------------------------------------------------------------ 4b. dense pseudo labels
+def _per_point(items, B, what, dtype, pts):
+    """B (N_b,) tensors of ``dtype``, one value per point of ``pts`` (``_on_gpu`` then checks the device)."""
+    items = list(items)
+    if len(items) != B:
+        raise ValueError(f"prepare_dense_pslabels: {len(items)} {what} arrays for {B} masks")
+    for t, p in zip(items, pts):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"prepare_dense_pslabels: {what} must be torch tensors on the GPU, got {type(t).__name__}")
+        if t.dtype != dtype or t.dim() != 1 or t.shape[0] != p.shape[0]:
+            raise ValueError(f"prepare_dense_pslabels: {what} must be {dtype} ({p.shape[0]},), got {t.dtype} {tuple(t.shape)}")
+    return items
+
+
+def prepare_dense_pslabels(probs, labels, points, masks, num_classes=10, max_area_thre=0.1, windows=None, flip=None, out=None,
+                           counts=None) -> torch.Tensor:
+    """``full_2d_pslabels`` of B SemanticKITTI target samples: what ``refine_sam_2Dlabels`` returns for the rows that
+    ``SemanticKITTISCN.preprocess`` expands (``semantic_kitti_dataloader.py:443-451``), then the crop ``windows`` and the ``flip``
+    of ``__getitem__`` -> (B, oh, ow) int32 with -100 for ignored pixels, which ``seg_ce`` takes against the flattened
+    ``seg_logit_all``.
+
+    Per sample: ``probs`` (N,) float32, the maximum probability per point; ``labels`` (N,) uint8, the raw pseudo labels;
+    ``points`` (N, 2) float [row, col] (``ori_img_points``); ``masks`` (H, W) uint8, the SAM mask as the file holds it (one size
+    per call).  The row of a point is ``(1 - p) / (num_classes - 1)`` everywhere and ``p`` at its label; the per-class median
+    refinement runs over the rows' maxima; the last point of a pixel wins it; every mask id below ``max_area_thre * H * W`` pixels
+    is filled with the first arg-max of its summed winning rows (class 0 without a reliable point), the other pixels keep the
+    refined label of their point or -100.  Equal to the reference on every id whose float64 sums decide it.
+
+    ``counts``: an optional (B,) int32 device tensor that receives, per sample, the points that were skipped (outside the image,
+    a label ``>= num_classes``, a probability outside [0, 1]; the reference raises on the first two).  No host synchronisation."""
+    ms = _image_list(masks, "masks", channels=0)
+    B, (H, W) = len(ms), ms[0].shape
+    if not isinstance(num_classes, (int, np.integer)) or not 2 <= num_classes <= 32:
+        raise ValueError(f"prepare_dense_pslabels: num_classes must be an int in [2, 32], got {num_classes!r}")
+    C = int(num_classes)
+    points = list(points)
+    if len(points) != B:
+        raise ValueError(f"prepare_dense_pslabels: {len(points)} point arrays for {B} masks")
+    for p in points:
+        if not isinstance(p, (np.ndarray, torch.Tensor)):
+            raise TypeError(f"prepare_dense_pslabels: points must be torch tensors on the GPU or numpy arrays, got {type(p).__name__}")
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"imageprep: points_img must be (N, 2) [row, col], got {tuple(p.shape)}")
+    pr = _per_point(probs, B, "probs", torch.float32, points)
+    lb = _per_point(labels, B, "labels", torch.uint8, points)
+    windows, oh, ow = _windows(windows, B, H, W)
+    flags = _flags(flip, B)
+    min_count = area_min_count(max_area_thre, H, W)
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, oh, ow) or out.dtype != torch.int32
+                            or not out.is_contiguous()):
+        raise ValueError(f"prepare_dense_pslabels: out must be a contiguous int32 {(B, oh, ow)} tensor on the masks' device")
+    if counts is not None and (not isinstance(counts, torch.Tensor) or tuple(counts.shape) != (B,) or counts.dtype != torch.int32
+                               or not counts.is_contiguous()):
+        raise ValueError(f"prepare_dense_pslabels: counts must be a contiguous int32 ({B},) tensor on the masks' device")
+    ms = _on_gpu(ms, "masks")
+    dev = ms[0].device
+    pr, lb = _on_gpu(pr, "probs"), _on_gpu(lb, "labels")
+    pts = _points(points)
+    for t in pts + pr + lb + [t for t in (out, counts) if t is not None]:
+        if _need_cuda(t, "every array").device != dev:
+            raise ValueError("prepare_dense_pslabels: every array of a call must be on the masks' device")
+    if out is None:
+        out = torch.empty(B, oh, ow, dtype=torch.int32, device=dev)
+    ns = [int(p.shape[0]) for p in pts]
+    for s, e in chunk_ranges(B, MAXB):
+        tabs = [host_ptrs(ts[s:e]) for ts in (pr, lb, pts, ms)]
+        n_host = host_i32(ns[s:e])
+        crop = host_i32([v for wd in windows[s:e] for v in (wd[1], wd[0])]) if windows else None
+        fl = None if flags is None else ctypes.addressof(flags) + 4 * s
+        ws = workspace.get(query("mopa_denselabels_workspace_bytes", e - s, H, W, sum(ns[s:e]), C), dev)
+        call("mopa_denselabels", host_addr(tabs[0]), host_addr(tabs[1]), host_addr(tabs[2]), 0 if pts[0].dtype == torch.float32 else 1,
+             host_addr(n_host), host_addr(tabs[3]), e - s, H, W, C, min_count, host_addr(crop), oh, ow, fl, ptr(out[s:e]),
+             None if counts is None else ptr(counts[s:e]), ptr(ws), ws.numel(), stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ 5. image indices
 def _points(points):
     """list of (N, 2) points -> contiguous float32 / float64 device tensors of one dtype (numpy arrays are uploaded; integer
@@ -471,14 +550,17 @@ def prepare_img_indices(points, src_size=None, size=None, windows=None, flip=Non
 
 
 # ------------------------------------------------------------------------------------------------ the batch
-def prepare_batch(samples, out=None, resize=None, normalizer=None, ema_input=False, max_area_thre=0.1) -> dict:
+def prepare_batch(samples, out=None, resize=None, normalizer=None, ema_input=False, max_area_thre=0.1, num_classes=10) -> dict:
     """The 2D side of one iteration's batch from the B raw samples, one launch per stage for all of them.
 
     ``samples``: B dicts with ``image`` (H, W, 3) uint8 and ``points_img`` (N, 2) float (device tensors; images of one size per
     call), optionally ``sam_mask`` (H, W) uint8, and the sample's draws: ``jitter`` = ``draw_color_jitter(...)`` or None, ``flip``
     = ``draw_flip(p)``, ``crop`` = ``draw_bottom_crop(...)`` (SemanticKITTI; all or none of a call), ``max_h`` (an int; default:
     from the points, ``h - int(min(points_img[:, 0]))``, reduced on the device).  ``resize`` = (w, h) as the dataset configs give
-    it (nuScenes, A2D2) or None.  ``out``: the (B, 3, h, w) float32 batch tensor to fill (allocated when None).
+    it (nuScenes, A2D2) or None.  ``out``: the (B, 3, h, w) float32 batch tensor to fill (allocated when None).  Samples with a
+    ``sam_mask`` may also carry ``probs_2d`` (N,) float32 and ``pseudo_label_2d`` (N,) uint8 (SemanticKITTI's pseudo-label form;
+    all or none of a call, not with a resize): the result then has ``full_2d_pslabels`` (list of (h, w) int32 with the crop and
+    flip of ``sam_mask_ls``; ``prepare_dense_pslabels`` with ``num_classes``) and nothing else changes.
 
     Returns ``img`` (B, 3, h, w), ``img_indices`` (list of (N', 2) int64), ``sam_mask_ls`` (list of (h, w) int32; when the samples
     carry masks), with ``ema_input`` ``ori_img`` (list of (3, h', w') float32: the resized -- SemanticKITTI: the uncropped --
@@ -503,6 +585,11 @@ def prepare_batch(samples, out=None, resize=None, normalizer=None, ema_input=Fal
         raise ValueError("prepare_batch: resize and crop in one call are not a form the datasets have")
     do_resize = resize is not None and tuple(resize) != (W, H)
     w, h = (int(resize[0]), int(resize[1])) if do_resize else (W, H)
+    has_ps = [s.get("probs_2d") is not None and s.get("pseudo_label_2d") is not None for s in samples]
+    if any(s.get("probs_2d") is not None or s.get("pseudo_label_2d") is not None for s in samples) and not all(has_ps):
+        raise ValueError("prepare_batch: either every sample of a call has probs_2d and pseudo_label_2d or none")
+    if has_ps[0] and (any(s.get("sam_mask") is None for s in samples) or do_resize):
+        raise ValueError("prepare_batch: probs_2d / pseudo_label_2d need a sam_mask and no resize (the SemanticKITTI form)")
     win, oh, ow = _windows(windows, B, h, w)
     _check_batch(out, (B, 3, oh, ow), None, "the batch tensor")      # every shape is checked before anything is launched
     imgs = _on_gpu(_image_list([s["image"] for s in samples]))
@@ -538,6 +625,11 @@ def prepare_batch(samples, out=None, resize=None, normalizer=None, ema_input=Fal
                                  max_h=None if need_min else [s["max_h"] for s in samples], row_min=ind.get("row_min"),
                                  max_area_thre=max_area_thre, windows=win, flip=flip)
         res["sam_mask_ls"] = list(masks.unbind(0))
+    if has_ps[0]:                                          # 4b. dense pseudo labels: the raw points on the unrefined mask
+        dense = prepare_dense_pslabels([s["probs_2d"] for s in samples], [s["pseudo_label_2d"] for s in samples],
+                                       [s["points_img"] for s in samples], [s["sam_mask"] for s in samples], num_classes=num_classes,
+                                       max_area_thre=max_area_thre, windows=win, flip=flip)
+        res["full_2d_pslabels"] = list(dense.unbind(0))
     idx = ind["img_indices"]
     if win is not None:
         keep = ind["keep"]
