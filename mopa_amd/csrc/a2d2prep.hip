@@ -11,7 +11,7 @@
 //                4-byte aligned (every group of a 1920-pixel row is), bytes otherwise (any width, any alignment, 1-pixel rows).
 //                No LDS: the map is smooth, so the 2 x 2 gathers of neighbouring threads fall into the same lines.
 //   k_a2_points  one thread per lidar point, all frames in one launch (a frame is cut into blocks of A2_ROWS points; per-frame
-//                pointers and the block table travel as kernel arguments, as in csrc/kittiprep.hip).  The label pixel is the
+//                pointers and the block table of segbatch.h travel as kernel arguments).  The label pixel is the
 //                remapped label image at (r, c) computed on the spot by the same a2_pixel as k_a2_remap -- the same bytes, and
 //                only N ~ 1e4 of 2.3 M label pixels are ever made.
 //
@@ -22,6 +22,7 @@
 // fx fy p11 + 512) >> 10, which is cv2.remap(INTER_LINEAR)'s 15-bit table form divided through by 32.  No float atomics; the one
 // counter (points outside the label image, per frame) is an integer; results are deterministic.
 #include "common.h"
+#include "segbatch.h"
 #include <limits.h>
 
 #pragma clang fp contract(off)
@@ -49,9 +50,7 @@ struct A2Frames {
   const double* col[A2_MAXB];
   const void* refl[A2_MAXB];        // (n,) uint8 / float32 / float64, or unused
   const uint8_t* label[A2_MAXB];    // (H, W, 3) uint8: the raw label image
-  int32_t n[A2_MAXB];
-  int32_t row0[A2_MAXB + 1];        // first point of the frame in the call's flat numbering
-  int32_t blk0[A2_MAXB + 1];        // first block of the frame
+  SegTable<A2_MAXB> seg;            // points and blocks of the call's flat numbering
 };
 
 // ------------------------------------------------------------------------------------------ the map
@@ -191,11 +190,6 @@ __global__ __launch_bounds__(256) void k_a2_remap(const A2Planes a, int P, int H
 }
 
 // ------------------------------------------------------------------------------------------ the points
-__device__ __forceinline__ int a2_segment(const int32_t* blk0, int S, int blk) {
-  int s = 0;
-  while (s + 1 < S && blk0[s + 1] <= blk) ++s;
-  return s;
-}
 // astype(np.int32) of a float64: truncation; what does not fit (or is not a number) lies outside every image
 __device__ __forceinline__ int a2_trunc(double v) { return v > -2147483649.0 && v < 2147483648.0 ? (int)v : INT_MIN; }
 
@@ -207,10 +201,10 @@ __global__ __launch_bounds__(A2_ROWS) void k_a2_points(const A2Frames a, int S, 
   __shared__ uint32_t tab[A2_MAXK];
   for (int k = threadIdx.x; k < K; k += A2_ROWS) tab[k] = table[3 * k] | table[3 * k + 1] << 8 | table[3 * k + 2] << 16;
   __syncthreads();
-  const int s = a2_segment(a.blk0, S, blockIdx.x);
-  const int i = (blockIdx.x - a.blk0[s]) * A2_ROWS + threadIdx.x;
-  if (i >= a.n[s]) return;
-  const int64_t o = (int64_t)a.row0[s] + i;
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int i = (blockIdx.x - a.seg.blk0[s]) * A2_ROWS + threadIdx.x;
+  if (i >= a.seg.n[s]) return;
+  const int64_t o = (int64_t)a.seg.row0[s] + i;
   const double rowd = a.row[s][i], cold = a.col[s][i];
   img[o] = make_float2((float)rowd, (float)cold);
   if (points_f64) {
@@ -288,16 +282,16 @@ MOPA_API int mopa_a2d2prep_points(const void* const* points_host, const void* co
                                   int32_t points_f64, int32_t refl_kind, const int16_t* xy, const uint16_t* frac, int32_t W, int32_t H,
                                   const uint8_t* table, int32_t K, float* points, float* feats, uint8_t* seg_labels, float* points_img,
                                   int32_t* bad, void* stream) {
-  if (!points_host || !row_host || !col_host || !label_host || !n_host || B < 1 || B > A2_MAXB) return MOPA_ERR_ARG;
+  A2Frames a = {};
+  const int blk = seg_table_fill(a.seg, n_host, B, A2_ROWS);
+  if (blk < 0 || !points_host || !row_host || !col_host || !label_host) return MOPA_ERR_ARG;
   if (refl_kind < 0 || refl_kind > 3 || (refl_kind && !refl_host) || (xy != nullptr) != (frac != nullptr)) return MOPA_ERR_ARG;
   if (W < 1 || H < 1 || W > A2_MAXSIDE || H > A2_MAXSIDE || K < 0 || K > A2_MAXK || (K > 0 && !table) || !bad) return MOPA_ERR_ARG;
   if (((uintptr_t)xy & 3) || ((uintptr_t)frac & 1) || ((uintptr_t)points_img & 7) || ((uintptr_t)points & 3) || ((uintptr_t)feats & 3)) return MOPA_ERR_ARG;
-  A2Frames a = {};
   const uintptr_t pmask = points_f64 ? 7 : 3, rmask = refl_kind == 3 ? 7 : refl_kind == 2 ? 3 : 0;
-  int64_t blk = 0, row = 0;
   for (int s = 0; s < B; ++s) {
     const int n = n_host[s];
-    if (n < 0 || !label_host[s]) return MOPA_ERR_ARG;
+    if (!label_host[s]) return MOPA_ERR_ARG;
     if (n > 0) {
       if (!points_host[s] || !row_host[s] || !col_host[s] || (refl_kind && !refl_host[s])) return MOPA_ERR_ARG;
       if (((uintptr_t)points_host[s] & pmask) || ((uintptr_t)row_host[s] & 7) || ((uintptr_t)col_host[s] & 7)) return MOPA_ERR_ARG;
@@ -308,15 +302,7 @@ MOPA_API int mopa_a2d2prep_points(const void* const* points_host, const void* co
     a.col[s] = (const double*)col_host[s];
     a.refl[s] = refl_kind ? refl_host[s] : nullptr;
     a.label[s] = (const uint8_t*)label_host[s];
-    a.n[s] = n;
-    a.row0[s] = (int32_t)row;
-    a.blk0[s] = (int32_t)blk;
-    blk += cdiv64(n, A2_ROWS);
-    row += n;
-    if (row >= (int64_t)1 << 30) return MOPA_ERR_ARG;
   }
-  a.row0[B] = (int32_t)row;
-  a.blk0[B] = (int32_t)blk;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(bad, 0, (size_t)B * sizeof(int32_t), st) != hipSuccess) return MOPA_ERR_LAUNCH;
   if (blk == 0) return MOPA_OK;

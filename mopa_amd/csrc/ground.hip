@@ -20,6 +20,7 @@
 //      eigenproblem: cyclic Jacobi, GR_SWEEPS sweeps, by one thread per workgroup.
 // Arithmetic is float64 after loading and is evaluated as written (no contraction into fused multiply-adds).
 #include "common.h"
+#include "segbatch.h"
 
 #pragma clang fp contract(off)
 
@@ -35,9 +36,6 @@
 #define GR_SWEEPS 10
 #define GR_NPARAM 18
 
-extern "C" int mopa_scan_exclusive_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* total, void* ws, size_t ws_bytes, void* stream);
-extern "C" size_t mopa_scan_workspace_bytes(int64_t n);
-
 struct GrParams {
   double h, rmin, rmax, th_seeds, th_dist, upright, noise_cut;
   double elev[4], flat[4];
@@ -48,16 +46,6 @@ __device__ __constant__ const int GR_RINGS[4] = {2, 4, 4, 4};
 __device__ __constant__ const int GR_SECTORS[4] = {16, 32, 54, 32};
 __device__ __constant__ const int GR_PATCH0[5] = {0, 32, 160, 376, 504};
 __device__ __constant__ const int GR_RING0[4] = {0, 2, 6, 10};
-
-// the scan of a block of passes 1 and 3: the last s with blk0[s] <= blk (empty scans share their successor's first block)
-__device__ __forceinline__ int gr_segment(const int32_t* __restrict__ blk0, int B, int blk) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (blk0[mid] <= blk) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ int gr_patch_of(float xf, float yf, float zf, const GrParams& P) {
   if (!(isfinite(xf) && isfinite(yf) && isfinite(zf))) return -1;
@@ -85,7 +73,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_gr_bin(const float* __restrict__
   __shared__ int hist[GR_PATCHES];
   const int32_t* row0 = tab;
   const int32_t* blk0 = tab + B + 1;
-  const int s = gr_segment(blk0, B, blockIdx.x);
+  const int s = seg_of_block(blk0, B, blockIdx.x);
   const int n = row0[s + 1] - row0[s];
   const int lb = blockIdx.x - blk0[s];
   const int nb = blk0[s + 1] <= (int)gridDim.x ? blk0[s + 1] - blk0[s] : 0;      // a table that names blocks past the grid is refused
@@ -120,7 +108,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_gr_order(const int32_t* __restri
   __shared__ int run[GR_PATCHES];
   const int32_t* row0 = tab;
   const int32_t* blk0 = tab + B + 1;
-  const int s = gr_segment(blk0, B, blockIdx.x);
+  const int s = seg_of_block(blk0, B, blockIdx.x);
   const int n = row0[s + 1] - row0[s];
   const int lb = blockIdx.x - blk0[s];
   const int nb = blk0[s + 1] <= (int)gridDim.x ? blk0[s + 1] - blk0[s] : 0;

@@ -4,9 +4,9 @@
 // preprocess do per sample on the host (mopa/data/semantic_kitti/semantic_kitti_dataloader.py:349-371,422-507 with
 // select_points_in_frustum :236-252).
 //
-// A fixed number of launches whatever B is: every kernel covers all scans of the call.  A scan is cut into blocks of KP_ROWS raw
-// rows; the host builds the block table (blk0[s] = first block of scan s), a block finds its scan from it.  Per-scan pointers
-// and matrices travel as kernel arguments (at most KP_MAXB scans per call; the binding splits larger batches).
+// A fixed number of launches whatever B is: every kernel covers all scans of the call, cut into blocks of KP_ROWS raw rows
+// (segbatch.h: the block table, the counts and their scan).  Per-scan pointers and matrices travel as kernel arguments (at most
+// KP_MAXB scans per call; the binding splits larger batches).
 //   1. k_kp_flags    one byte per raw row (bit 0: z > -3, bit 1: kept) and per block the two counts
 //   2. ordered exclusive scan of the counts (mopa_scan_exclusive_i32), then k_kp_counts: [Nz, Nk] per scan for the one read-back
 //   3. k_kp_scatter  every output, rows in the order of the scan
@@ -19,18 +19,14 @@
 // comparisons are IEEE (a NaN from 0/0 and an infinity from x/0 fail them and the row is dropped).  No float atomics; counts are
 // integers and the compaction is ordered -> deterministic.
 #include "common.h"
+#include "segbatch.h"
 
 #define KP_MAXB 32             // scans per call
 #define KP_ROWS 1024           // raw rows per block (256 threads x 4 tiles)
 
-extern "C" int mopa_scan_exclusive_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* total, void* ws, size_t ws_bytes, void* stream);
-extern "C" size_t mopa_scan_workspace_bytes(int64_t n);
-
 struct KpSeg {
   const float4* scan[KP_MAXB];      // (n, 4) float32: x, y, z, remission
-  int32_t n[KP_MAXB];
-  int32_t row0[KP_MAXB + 1];        // first row of the scan in the call's flat raw numbering
-  int32_t blk0[KP_MAXB + 1];        // first block of the scan
+  SegTable<KP_MAXB> seg;            // rows and blocks of the call's flat raw numbering
 };
 struct KpProj {
   float m[KP_MAXB][12];             // proj_matrix (3, 4), row-major
@@ -43,8 +39,7 @@ struct KpMask {
 struct KpGround {
   const int32_t* idx[KP_MAXB];      // (g,) indices into the raw scan
   int32_t g[KP_MAXB];
-  int32_t n[KP_MAXB];
-  int32_t row0[KP_MAXB];
+  SegTable<KP_MAXB> seg;
 };
 struct KpOut {
   const void* label[KP_MAXB];       // (n,) int32 / int64: the label file as loaded
@@ -58,11 +53,6 @@ struct KpOut {
   int16_t* all_seg;                 // (Nz,) or null
 };
 
-__device__ __forceinline__ int kp_segment(const int32_t* blk0, int S, int blk) {
-  int s = 0;
-  while (s + 1 < S && blk0[s + 1] <= blk) ++s;
-  return s;
-}
 // img_points of one front-half point, rounded to cents, and the frustum test (u: column, v: row)
 __device__ __forceinline__ bool kp_project(const float* m, float w, float h, float x, float y, float z, float& u, float& v) {
   float p[3];
@@ -73,42 +63,19 @@ __device__ __forceinline__ bool kp_project(const float* m, float w, float h, flo
   v = __fdiv_rn(rintf(__fmul_rn(__fdiv_rn(p[1], p[2]), 100.f)), 100.f);
   return u > 0.f && v > 0.f && u < w && v < h;
 }
-// rank of the thread among the block's threads with p, in thread order, and their number
-__device__ __forceinline__ int kp_rank(bool p, int* lds, int& total) {
-  const unsigned long long m = __ballot(p);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) lds[w] = __popcll(m);
-  __syncthreads();
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int c = lds[k]; pre += k < w ? c : 0; tot += c; }
-  __syncthreads();
-  total = tot;
-  return pre + r;
-}
-__device__ __forceinline__ void kp_block_counts(int cz, int ck, int* cnt, int nblk, bool z_too) {
-  __shared__ int red[4][2];
-  cz = wave_sum_i(cz);
-  ck = wave_sum_i(ck);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = cz; red[threadIdx.x >> 6][1] = ck; }
-  __syncthreads();
-  if (threadIdx.x < 2 && (z_too || threadIdx.x == 1))
-    cnt[threadIdx.x * nblk + blockIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
 
 // ------------------------------------------------------------------------------------------ 1. flags + block counts
 // cnt[blk] = rows of the block with z > -3, cnt[nblk + blk] = kept rows of the block (0 without `project`: k_kp_mask sets them)
 __global__ __launch_bounds__(256) void k_kp_flags(const KpSeg a, const KpProj pj, int S, int project, uint8_t* __restrict__ flags,
                                                   int* __restrict__ cnt, int nblk) {
-  const int s = kp_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s];
   const float4* __restrict__ scan = a.scan[s];
   float m[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) m[k] = pj.m[s][k];
-  const int base = (blockIdx.x - a.blk0[s]) * KP_ROWS;
-  int cz = 0, ck = 0;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * KP_ROWS;
+  int c[2] = {0, 0};                // rows with z > -3, kept rows
 #pragma unroll
   for (int t = 0; t < KP_ROWS / 256; ++t) {
     const int i = base + t * 256 + threadIdx.x;
@@ -117,39 +84,39 @@ __global__ __launch_bounds__(256) void k_kp_flags(const KpSeg a, const KpProj pj
       const bool zf = q.z > -3.f;
       bool kept = false;
       if (project && zf && q.x > 0.f) { float u, v; kept = kp_project(m, pj.w, pj.h, q.x, q.y, q.z, u, v); }
-      flags[(int64_t)a.row0[s] + i] = (uint8_t)((zf ? 1 : 0) | (kept ? 2 : 0));
-      cz += zf;
-      ck += kept;
+      flags[(int64_t)a.seg.row0[s] + i] = (uint8_t)((zf ? 1 : 0) | (kept ? 2 : 0));
+      c[0] += zf;
+      c[1] += kept;
     }
   }
-  kp_block_counts(cz, ck, cnt, nblk, true);
+  block_counts(c, cnt, nblk);
 }
 // The pseudo-label form: bit 1 of a z-filtered row = mask[its position in the z-filtered scan] (false past the mask's end: the
 // binding refuses a mask of another length after the read-back).  scan = exclusive scan of cnt after k_kp_flags.
 __global__ __launch_bounds__(256) void k_kp_mask(const KpSeg a, const KpMask mk, int S, uint8_t* __restrict__ flags,
                                                  const int* __restrict__ scan, int* __restrict__ cnt, int nblk) {
   __shared__ int lds[4];
-  const int s = kp_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s];
   const uint8_t* __restrict__ mask = mk.mask[s];
   const int len = mk.len[s];
-  const int base = (blockIdx.x - a.blk0[s]) * KP_ROWS;
-  int run = scan[blockIdx.x] - scan[a.blk0[s]];
-  int ck = 0;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * KP_ROWS;
+  int run = scan[blockIdx.x] - scan[a.seg.blk0[s]];
+  int c[2] = {0, 0};
 #pragma unroll
   for (int t = 0; t < KP_ROWS / 256; ++t) {
     const int i = base + t * 256 + threadIdx.x;
-    const int64_t row = (int64_t)a.row0[s] + i;
+    const int64_t row = (int64_t)a.seg.row0[s] + i;
     const bool zf = i < n && (flags[row] & 1);
     int tot;
-    const int r = kp_rank(zf, lds, tot);
+    const int r = block_rank<256>(zf, lds, tot);
     if (zf) {
       const int zp = run + r;
-      if (zp < len && mask[zp]) { flags[row] = 3; ++ck; }
+      if (zp < len && mask[zp]) { flags[row] = 3; ++c[1]; }
     }
     run += tot;
   }
-  kp_block_counts(0, ck, cnt, nblk, false);
+  block_counts(c, cnt, nblk, 2u);   // the kept plane only
 }
 // counts[2 s] = Nz, counts[2 s + 1] = Nk of scan s; counts[2 S] = ground indices outside their scan.  blk0[S] = nblk, and the
 // scan has one item more than counts: scan[2 nblk] is the grand total.
@@ -157,8 +124,8 @@ __global__ void k_kp_counts(const KpSeg a, int S, const int* __restrict__ scan, 
                             int64_t* __restrict__ counts) {
   const int i = threadIdx.x;
   if (i < S) {
-    counts[2 * i] = scan[a.blk0[i + 1]] - scan[a.blk0[i]];
-    counts[2 * i + 1] = scan[nblk + a.blk0[i + 1]] - scan[nblk + a.blk0[i]];
+    counts[2 * i] = scan[a.seg.blk0[i + 1]] - scan[a.seg.blk0[i]];
+    counts[2 * i + 1] = scan[nblk + a.seg.blk0[i + 1]] - scan[nblk + a.seg.blk0[i]];
   }
   if (i == S) counts[2 * S] = bad ? *bad : 0;
 }
@@ -167,13 +134,13 @@ __global__ void k_kp_counts(const KpSeg a, int S, const int* __restrict__ scan, 
 // g_mask = zeros(n); g_mask[g_indices] = 1 (numpy's indexing: a negative index counts from the end; one outside is counted)
 __global__ __launch_bounds__(256) void k_kp_ground(const KpGround a, uint8_t* __restrict__ gmask, int* __restrict__ bad) {
   const int s = blockIdx.y;
-  const int g = a.g[s], n = a.n[s];
+  const int g = a.g[s], n = a.seg.n[s];
   const int32_t* __restrict__ idx = a.idx[s];
   for (int j = blockIdx.x * 256 + threadIdx.x; j < g; j += gridDim.x * 256) {
     int64_t k = idx[j];
     if (k < 0) k += n;
     if (k < 0 || k >= n) atomicAdd(bad, 1);
-    else gmask[(int64_t)a.row0[s] + k] = 1;
+    else gmask[(int64_t)a.seg.row0[s] + k] = 1;
   }
 }
 
@@ -184,23 +151,23 @@ __global__ __launch_bounds__(256) void k_kp_scatter(const KpSeg a, const KpProj 
                                                     const uint8_t* __restrict__ flags, const uint8_t* __restrict__ gmask,
                                                     const int* __restrict__ scan, int nblk) {
   __shared__ int lds[4];
-  const int s = kp_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s];
   const float4* __restrict__ src = a.scan[s];
   const void* label = o.label[s];
   float m[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) m[k] = pj.m[s][k];
-  const int base = (blockIdx.x - a.blk0[s]) * KP_ROWS;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * KP_ROWS;
   int64_t runz = scan[blockIdx.x], runk = (int64_t)scan[nblk + blockIdx.x] - scan[nblk];
 #pragma unroll
   for (int t = 0; t < KP_ROWS / 256; ++t) {
     const int i = base + t * 256 + threadIdx.x;
-    const int64_t row = (int64_t)a.row0[s] + i;
+    const int64_t row = (int64_t)a.seg.row0[s] + i;
     const uint8_t fl = i < n ? flags[row] : 0;
     int totz, totk;
-    const int rz = kp_rank(fl & 1, lds, totz);
-    const int rk = kp_rank(fl & 2, lds, totk);
+    const int rz = block_rank<256>(fl & 1, lds, totz);
+    const int rk = block_rank<256>(fl & 2, lds, totk);
     if (fl & 1) {
       const float4 q = src[i];
       const int64_t raw = label_i64 ? ((const int64_t*)label)[i] : (int64_t)((const int32_t*)label)[i];
@@ -230,22 +197,14 @@ __global__ __launch_bounds__(256) void k_kp_scatter(const KpSeg a, const KpProj 
 }
 
 // ------------------------------------------------------------------------------------------ entry points
-static int kp_fill(KpSeg& a, const void* const* scan_host, const int32_t* n_host, int B) {
-  if (!scan_host || !n_host || B < 1 || B > KP_MAXB) return -1;
-  int64_t blk = 0, row = 0;
+static int kp_scans(KpSeg& a, const void* const* scan_host, const int32_t* n_host, int B) {
+  const int nblk = seg_table_fill(a.seg, n_host, B, KP_ROWS);
+  if (nblk < 0 || !scan_host) return -1;
   for (int s = 0; s < B; ++s) {
-    if (n_host[s] < 0 || (n_host[s] > 0 && (!scan_host[s] || ((uintptr_t)scan_host[s] & 15)))) return -1;
+    if (n_host[s] > 0 && (!scan_host[s] || ((uintptr_t)scan_host[s] & 15))) return -1;
     a.scan[s] = (const float4*)scan_host[s];
-    a.n[s] = n_host[s];
-    a.row0[s] = (int32_t)row;
-    a.blk0[s] = (int32_t)blk;
-    blk += cdiv64(n_host[s], KP_ROWS);
-    row += n_host[s];
-    if (row >= (int64_t)1 << 30) return -1;
   }
-  a.row0[B] = (int32_t)row;
-  a.blk0[B] = (int32_t)blk;
-  return (int)blk;
+  return nblk;
 }
 static void kp_proj(KpProj& pj, const float* proj_host, int B, int width, int height) {
   for (int s = 0; s < B; ++s)
@@ -256,29 +215,24 @@ static void kp_proj(KpProj& pj, const float* proj_host, int B, int width, int he
 
 MOPA_API int mopa_kittiprep_rows_per_block(void) { return KP_ROWS; }
 MOPA_API int mopa_kittiprep_max_scans(void) { return KP_MAXB; }
-// workspace: cnt [2 nblk + 1] | scan [2 nblk + 1] | total | scratch of the scan
-static size_t kp_ws_ints(int64_t nblk) { return (size_t)(4 * nblk + 16); }
+// workspace: the two count planes (z > -3, kept) of segbatch.h's SegCounts
 MOPA_API size_t mopa_kittiprep_workspace_bytes(int64_t total_blocks) {
   if (total_blocks < 0) return 0;
-  return align_up(kp_ws_ints(total_blocks) * sizeof(int), 256) + mopa_scan_workspace_bytes(2 * total_blocks + 1);
+  return seg_counts_bytes(2, total_blocks);
 }
 
 // The ground mask of B scans over the call's flat raw numbering: gmask (sum n bytes) is cleared, then gmask[row0[s] + i] = 1 for
 // every i of gidx_host[s] (g_host[s] int32 indices into scan s); *bad = number of indices outside their scan.
 MOPA_API int mopa_kittiprep_ground(const void* const* gidx_host, const int32_t* g_host, const int32_t* n_host, int32_t B, uint8_t* gmask,
                                    int32_t* bad, void* stream) {
-  if (!gidx_host || !g_host || !n_host || B < 1 || B > KP_MAXB || !gmask || !bad) return MOPA_ERR_ARG;
   KpGround a = {};
-  int64_t row = 0;
+  if (!gidx_host || !g_host || seg_table_fill(a.seg, n_host, B, KP_ROWS) < 0 || !gmask || !bad) return MOPA_ERR_ARG;
+  const int64_t row = a.seg.row0[B];
   int gmax = 0;
   for (int s = 0; s < B; ++s) {
-    if (n_host[s] < 0 || g_host[s] < 0 || (g_host[s] > 0 && !gidx_host[s])) return MOPA_ERR_ARG;
+    if (g_host[s] < 0 || (g_host[s] > 0 && !gidx_host[s])) return MOPA_ERR_ARG;
     a.idx[s] = (const int32_t*)gidx_host[s];
     a.g[s] = g_host[s];
-    a.n[s] = n_host[s];
-    a.row0[s] = (int32_t)row;
-    row += n_host[s];
-    if (row >= (int64_t)1 << 30) return MOPA_ERR_ARG;
     gmax = g_host[s] > gmax ? g_host[s] : gmax;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -299,7 +253,7 @@ MOPA_API int mopa_kittiprep_count(const void* const* scan_host, const int32_t* n
                                   const int32_t* mask_n_host, int32_t B, int32_t width, int32_t height, uint8_t* flags, const int32_t* bad,
                                   int64_t* counts, void* ws, size_t ws_bytes, void* stream) {
   KpSeg a = {};
-  const int nblk = kp_fill(a, scan_host, n_host, B);
+  const int nblk = kp_scans(a, scan_host, n_host, B);
   if (nblk < 0 || !flags || !counts || !ws || (proj_host != nullptr) == (mask_host != nullptr) || (mask_host && !mask_n_host)) return MOPA_ERR_ARG;
   if (proj_host && (width <= 0 || height <= 0)) return MOPA_ERR_ARG;
   if (ws_bytes < mopa_kittiprep_workspace_bytes(nblk)) return MOPA_ERR_WORKSPACE;
@@ -313,22 +267,17 @@ MOPA_API int mopa_kittiprep_count(const void* const* scan_host, const int32_t* n
       mk.len[s] = mask_n_host[s];
     }
   hipStream_t st = (hipStream_t)stream;
-  int* cnt = (int*)ws;
-  int* scan = cnt + 2 * nblk + 1;
-  int* tot = scan + 2 * nblk + 1;
-  void* sws = (char*)ws + align_up(kp_ws_ints(nblk) * sizeof(int), 256);
-  const size_t sws_bytes = mopa_scan_workspace_bytes(2 * nblk + 1);
-  // the kept counts of the pseudo-label form stay zero until k_kp_mask; one more (zero) item so that scan[2 nblk] exists
-  if (hipMemsetAsync(cnt, 0, (size_t)(2 * nblk + 1) * sizeof(int), st) != hipSuccess) return MOPA_ERR_LAUNCH;
-  if (nblk > 0) k_kp_flags<<<nblk, 256, 0, st>>>(a, pj, B, proj_host != nullptr, flags, cnt, nblk);
-  int rc = mopa_scan_exclusive_i32(cnt, scan, 2 * nblk + 1, tot, sws, sws_bytes, stream);
+  const SegCounts c = seg_counts(ws, 2, nblk);
+  // the kept counts of the pseudo-label form are zero until k_kp_mask
+  if (nblk > 0) k_kp_flags<<<nblk, 256, 0, st>>>(a, pj, B, proj_host != nullptr, flags, c.cnt, nblk);
+  int rc = seg_counts_scan(c, stream);
   if (rc) return rc;
   if (mask_host && nblk > 0) {
-    k_kp_mask<<<nblk, 256, 0, st>>>(a, mk, B, flags, scan, cnt, nblk);
-    rc = mopa_scan_exclusive_i32(cnt, scan, 2 * nblk + 1, tot, sws, sws_bytes, stream);
+    k_kp_mask<<<nblk, 256, 0, st>>>(a, mk, B, flags, c.scan, c.cnt, nblk);
+    rc = seg_counts_scan(c, stream, false);
     if (rc) return rc;
   }
-  k_kp_counts<<<1, 64, 0, st>>>(a, B, scan, nblk, bad, counts);
+  k_kp_counts<<<1, 64, 0, st>>>(a, B, c.scan, nblk, bad, counts);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }
@@ -343,7 +292,7 @@ MOPA_API int mopa_kittiprep_scatter(const void* const* scan_host, const void* co
                                     uint8_t* ori_keep_idx, uint8_t* g_out, float* full_scan, int16_t* all_seg, void* ws, size_t ws_bytes,
                                     void* stream) {
   KpSeg a = {};
-  const int nblk = kp_fill(a, scan_host, n_host, B);
+  const int nblk = kp_scans(a, scan_host, n_host, B);
   if (nblk < 0 || !label_host || !flags || !points || !feats || !seg_labels || !ori_keep_idx || !ws) return MOPA_ERR_ARG;
   if ((proj_host != nullptr) != (points_img != nullptr) || (gmask != nullptr) != (g_out != nullptr) || (full_scan != nullptr) != (all_seg != nullptr))
     return MOPA_ERR_ARG;
@@ -359,8 +308,7 @@ MOPA_API int mopa_kittiprep_scatter(const void* const* scan_host, const void* co
   o.points = points; o.feats = feats; o.seg = seg_labels; o.img = (float2*)points_img; o.keep = ori_keep_idx; o.ground = g_out;
   o.full_scan = full_scan; o.all_seg = all_seg;
   if (nblk == 0) return MOPA_OK;
-  const int* scan = (const int*)ws + 2 * nblk + 1;
-  k_kp_scatter<<<nblk, 256, 0, (hipStream_t)stream>>>(a, pj, o, B, label_i64, flags, gmask, scan, nblk);
+  k_kp_scatter<<<nblk, 256, 0, (hipStream_t)stream>>>(a, pj, o, B, label_i64, flags, gmask, seg_counts(ws, 2, nblk).scan, nblk);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }

@@ -4,8 +4,8 @@
 // (mopa/data/nuscenes/preprocess.py:116-126 with the devkit's points_in_box), ONE stable compaction of every per-point array
 // (preprocess.py:111-114) and the ground mask of the dataset (mopa/data/nuscenes/nuscenes_dataloader.py:305-316).
 //
-// A fixed number of launches whatever B and the number of boxes are: every kernel covers all scans of the call.  A scan is cut
-// into blocks of NP_ROWS raw rows; the host builds the block table, a block finds its scan from it (as csrc/kittiprep.hip).
+// A fixed number of launches whatever B and the number of boxes are: every kernel covers all scans of the call, cut into blocks
+// of NP_ROWS raw rows (segbatch.h: the block table, the counts and their scan).
 //   0. k_np_setup    one thread per quaternion or box: a small device table (NP_SCAN doubles per scan: four rotation matrices,
 //                    four translations, the 4x4 viewpad; NP_BOX doubles per box: p1, i, j, k, dot(i,i), dot(j,j), dot(k,k), the
 //                    class, the rotation matrix).  The per-scan constants of 32 scans do not fit a kernel-argument block, and
@@ -23,6 +23,7 @@
 // depth > 0 is tested in float64.  All of it is spelled with __fma_rn / __dmul_rn / __dadd_rn / __dsub_rn / __ddiv_rn: the compiler
 // contracts nothing on its own.  No float atomics; counts are integers and the compaction is ordered -> deterministic.
 #include "common.h"
+#include "segbatch.h"
 
 #define NP_MAXB 32             // scans per call
 #define NP_ROWS 1024           // raw rows per block (256 threads x 4 tiles)
@@ -34,23 +35,13 @@
 #define NP_FRAME 16            // p1 | i | j | k | ii, jj, kk | class
 #define NP_BOX 25              // frame | R[9]
 
-extern "C" int mopa_scan_exclusive_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* total, void* ws, size_t ws_bytes, void* stream);
-extern "C" size_t mopa_scan_workspace_bytes(int64_t n);
-
 struct NpSeg {
   const float* scan[NP_MAXB];       // (n, cols) float32, x y z first
-  int32_t n[NP_MAXB];
+  SegTable<NP_MAXB> seg;            // rows and blocks of the call's flat raw numbering
   int32_t cols[NP_MAXB];
-  int32_t row0[NP_MAXB + 1];        // first row of the scan in the call's flat raw numbering
-  int32_t blk0[NP_MAXB + 1];        // first block of the scan
   int32_t box0[NP_MAXB + 1];        // first box of the scan in the call's box list
 };
 
-__device__ __forceinline__ int np_segment(const int32_t* blk0, int S, int blk) {
-  int s = 0;
-  while (s + 1 < S && blk0[s + 1] <= blk) ++s;
-  return s;
-}
 __device__ __forceinline__ double np_dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
   return __fma_rn(a2, b2, __fma_rn(a1, b1, __dmul_rn(a0, b0)));
 }
@@ -138,33 +129,18 @@ __device__ __forceinline__ bool np_project(const double* __restrict__ t, float w
   v = (float)__ddiv_rn(hh[1], hh[2]);
   return p[2] > 0.0 && u > 0.f && u < w && v > 0.f && v < h;
 }
-// rank of the thread among the block's threads with p, in thread order, and their number
-__device__ __forceinline__ int np_rank(bool p, int* lds, int& total) {
-  const unsigned long long m = __ballot(p);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) lds[w] = __popcll(m);
-  __syncthreads();
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int c = lds[k]; pre += k < w ? c : 0; tot += c; }
-  __syncthreads();
-  total = tot;
-  return pre + r;
-}
 
 // ------------------------------------------------------------------------------------------ 1. flags + block counts
 // A raw row is `cols` floats (5 in a .pcd.bin: 20 bytes, so rows are only 4-byte aligned): three scalar loads per thread; the
 // 64 rows of a wave lie in one contiguous stretch, so the three loads hit the same lines.
 __global__ __launch_bounds__(256) void k_np_flags(const NpSeg a, int S, const double* __restrict__ table, float w, float h,
                                                   uint8_t* __restrict__ flags, int* __restrict__ cnt) {
-  __shared__ int red[4];
-  const int s = np_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s], cols = a.cols[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s], cols = a.cols[s];
   const float* __restrict__ scan = a.scan[s];
   const double* __restrict__ t = table + (int64_t)s * NP_SCAN;
-  const int base = (blockIdx.x - a.blk0[s]) * NP_ROWS;
-  int ck = 0;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * NP_ROWS;
+  int c[1] = {0};
 #pragma unroll
   for (int tile = 0; tile < NP_TILES; ++tile) {
     const int i = base + tile * 256 + threadIdx.x;
@@ -172,19 +148,16 @@ __global__ __launch_bounds__(256) void k_np_flags(const NpSeg a, int S, const do
       const float* row = scan + (int64_t)i * cols;
       float u, v;
       const bool kept = np_project(t, w, h, row[0], row[1], row[2], u, v);
-      flags[(int64_t)a.row0[s] + i] = kept ? 1 : 0;
-      ck += kept;
+      flags[(int64_t)a.seg.row0[s] + i] = kept ? 1 : 0;
+      c[0] += kept;
     }
   }
-  ck = wave_sum_i(ck);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ck;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  block_counts(c, cnt, gridDim.x);
 }
 // counts[s] = Nk of scan s; counts[S] = ground indices outside their scan.  scan has nblk + 1 items: scan[nblk] is the total.
 __global__ void k_np_counts(const NpSeg a, int S, const int* __restrict__ scan, const int* __restrict__ bad, int64_t* __restrict__ counts) {
   const int i = threadIdx.x;
-  if (i < S) counts[i] = scan[a.blk0[i + 1]] - scan[a.blk0[i]];
+  if (i < S) counts[i] = scan[a.seg.blk0[i + 1]] - scan[a.seg.blk0[i]];
   if (i == S) counts[S] = bad ? *bad : 0;
 }
 
@@ -195,20 +168,20 @@ __global__ __launch_bounds__(256) void k_np_scatter(const NpSeg a, int S, const 
                                                     uint8_t* __restrict__ seg, uint8_t* __restrict__ ground) {
   __shared__ int lds[4];
   __shared__ double frames[NP_LDS_BOXES * NP_FRAME];
-  const int s = np_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s], cols = a.cols[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s], cols = a.cols[s];
   const float* __restrict__ src = a.scan[s];
   const double* __restrict__ t = table + (int64_t)s * NP_SCAN;
   const double* __restrict__ boxes = table + (int64_t)S * NP_SCAN + (int64_t)a.box0[s] * NP_BOX;
   const int m = a.box0[s + 1] - a.box0[s];
-  const int base = (blockIdx.x - a.blk0[s]) * NP_ROWS;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * NP_ROWS;
   float x[NP_TILES], y[NP_TILES], z[NP_TILES];
   bool kept[NP_TILES];
   int label[NP_TILES];
 #pragma unroll
   for (int tile = 0; tile < NP_TILES; ++tile) {
     const int i = base + tile * 256 + threadIdx.x;
-    kept[tile] = i < n && flags[(int64_t)a.row0[s] + i];
+    kept[tile] = i < n && flags[(int64_t)a.seg.row0[s] + i];
     label[tile] = 10;
     x[tile] = y[tile] = z[tile] = 0.f;
     if (kept[tile]) {
@@ -240,7 +213,7 @@ __global__ __launch_bounds__(256) void k_np_scatter(const NpSeg a, int S, const 
 #pragma unroll
   for (int tile = 0; tile < NP_TILES; ++tile) {
     int tot;
-    const int r = np_rank(kept[tile], lds, tot);
+    const int r = block_rank<256>(kept[tile], lds, tot);
     if (kept[tile]) {
       const int64_t kp = run + r;
       points[3 * kp] = x[tile]; points[3 * kp + 1] = y[tile]; points[3 * kp + 2] = z[tile];
@@ -248,30 +221,22 @@ __global__ __launch_bounds__(256) void k_np_scatter(const NpSeg a, int S, const 
       np_project(t, w, h, x[tile], y[tile], z[tile], u, v);
       img[kp] = make_float2(v, u);                       // the reference's fliplr: [row, col]
       seg[kp] = (uint8_t)label[tile];
-      if (ground) ground[kp] = gmask[(int64_t)a.row0[s] + base + tile * 256 + threadIdx.x];
+      if (ground) ground[kp] = gmask[(int64_t)a.seg.row0[s] + base + tile * 256 + threadIdx.x];
     }
     run += tot;
   }
 }
 
 // ------------------------------------------------------------------------------------------ entry points
-static int np_fill(NpSeg& a, const void* const* scan_host, const int32_t* n_host, const int32_t* cols_host, int B) {
-  if (!scan_host || !n_host || !cols_host || B < 1 || B > NP_MAXB) return -1;
-  int64_t blk = 0, row = 0;
+static int np_scans(NpSeg& a, const void* const* scan_host, const int32_t* n_host, const int32_t* cols_host, int B) {
+  const int nblk = seg_table_fill(a.seg, n_host, B, NP_ROWS);
+  if (nblk < 0 || !scan_host || !cols_host) return -1;
   for (int s = 0; s < B; ++s) {
-    if (n_host[s] < 0 || cols_host[s] < 3 || (n_host[s] > 0 && (!scan_host[s] || ((uintptr_t)scan_host[s] & 3)))) return -1;
+    if (cols_host[s] < 3 || (n_host[s] > 0 && (!scan_host[s] || ((uintptr_t)scan_host[s] & 3)))) return -1;
     a.scan[s] = (const float*)scan_host[s];
-    a.n[s] = n_host[s];
     a.cols[s] = cols_host[s];
-    a.row0[s] = (int32_t)row;
-    a.blk0[s] = (int32_t)blk;
-    blk += cdiv64(n_host[s], NP_ROWS);
-    row += n_host[s];
-    if (row >= (int64_t)1 << 30) return -1;
   }
-  a.row0[B] = (int32_t)row;
-  a.blk0[B] = (int32_t)blk;
-  return (int)blk;
+  return nblk;
 }
 
 MOPA_API int mopa_nuscprep_rows_per_block(void) { return NP_ROWS; }
@@ -283,11 +248,10 @@ MOPA_API size_t mopa_nuscprep_table_bytes(int32_t B, int64_t M) {
   if (B < 0 || M < 0) return 0;
   return ((size_t)B * NP_SCAN + (size_t)M * NP_BOX) * sizeof(double);
 }
-// workspace: cnt [nblk + 1] | scan [nblk + 1] | total | scratch of the scan
-static size_t np_ws_ints(int64_t nblk) { return (size_t)(2 * nblk + 16); }
+// workspace: the one count plane (kept rows) of segbatch.h's SegCounts
 MOPA_API size_t mopa_nuscprep_workspace_bytes(int64_t total_blocks) {
   if (total_blocks < 0) return 0;
-  return align_up(np_ws_ints(total_blocks) * sizeof(int), 256) + mopa_scan_workspace_bytes(total_blocks + 1);
+  return seg_counts_bytes(1, total_blocks);
 }
 
 // Stage 0.  calib (B, 37) float64 on the device: per scan the four quaternions wxyz (lidar2ego, ego2global of the lidar's pose,
@@ -309,20 +273,15 @@ MOPA_API int mopa_nuscprep_count(const void* const* scan_host, const int32_t* n_
                                  int32_t width, int32_t height, uint8_t* flags, const int32_t* bad, int64_t* counts, void* ws,
                                  size_t ws_bytes, void* stream) {
   NpSeg a = {};
-  const int nblk = np_fill(a, scan_host, n_host, cols_host, B);
+  const int nblk = np_scans(a, scan_host, n_host, cols_host, B);
   if (nblk < 0 || !table || !flags || !counts || !ws || width <= 0 || height <= 0) return MOPA_ERR_ARG;
   if (ws_bytes < mopa_nuscprep_workspace_bytes(nblk)) return MOPA_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  int* cnt = (int*)ws;
-  int* scan = cnt + nblk + 1;
-  int* tot = scan + nblk + 1;
-  void* sws = (char*)ws + align_up(np_ws_ints(nblk) * sizeof(int), 256);
-  // one more (zero) item so that scan[nblk] exists
-  if (hipMemsetAsync(cnt, 0, (size_t)(nblk + 1) * sizeof(int), st) != hipSuccess) return MOPA_ERR_LAUNCH;
-  if (nblk > 0) k_np_flags<<<nblk, 256, 0, st>>>(a, B, table, (float)width, (float)height, flags, cnt);
-  const int rc = mopa_scan_exclusive_i32(cnt, scan, nblk + 1, tot, sws, mopa_scan_workspace_bytes(nblk + 1), stream);
+  const SegCounts c = seg_counts(ws, 1, nblk);
+  if (nblk > 0) k_np_flags<<<nblk, 256, 0, st>>>(a, B, table, (float)width, (float)height, flags, c.cnt);
+  const int rc = seg_counts_scan(c, stream);
   if (rc) return rc;
-  k_np_counts<<<1, 64, 0, st>>>(a, B, scan, bad, counts);
+  k_np_counts<<<1, 64, 0, st>>>(a, B, c.scan, bad, counts);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }
@@ -336,7 +295,7 @@ MOPA_API int mopa_nuscprep_scatter(const void* const* scan_host, const int32_t* 
                                    float* points, float* points_img, uint8_t* seg_labels, uint8_t* g_out, void* ws, size_t ws_bytes,
                                    void* stream) {
   NpSeg a = {};
-  const int nblk = np_fill(a, scan_host, n_host, cols_host, B);
+  const int nblk = np_scans(a, scan_host, n_host, cols_host, B);
   if (nblk < 0 || !boxoff_host || !table || !flags || !points || !points_img || !seg_labels || !ws || width <= 0 || height <= 0) return MOPA_ERR_ARG;
   if ((gmask != nullptr) != (g_out != nullptr) || ((uintptr_t)points_img & 7)) return MOPA_ERR_ARG;
   if (boxoff_host[0] != 0) return MOPA_ERR_ARG;
@@ -346,8 +305,7 @@ MOPA_API int mopa_nuscprep_scatter(const void* const* scan_host, const int32_t* 
   }
   if (ws_bytes < mopa_nuscprep_workspace_bytes(nblk)) return MOPA_ERR_WORKSPACE;
   if (nblk == 0) return MOPA_OK;
-  const int* scan = (const int*)ws + nblk + 1;
-  k_np_scatter<<<nblk, 256, 0, (hipStream_t)stream>>>(a, B, table, (float)width, (float)height, flags, gmask, scan, points,
+  k_np_scatter<<<nblk, 256, 0, (hipStream_t)stream>>>(a, B, table, (float)width, (float)height, flags, gmask, seg_counts(ws, 1, nblk).scan, points,
                                                      (float2*)points_img, seg_labels, g_out);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;

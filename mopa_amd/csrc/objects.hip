@@ -32,6 +32,7 @@
 //                    ranges in a fixed order (per thread in position order, a fixed shuffle tree, the waves in order), the table row
 // d2 = (dx dx + dy dy) + dz dz in float64 from the float32 inputs, evaluated as written (no contraction).
 #include "common.h"
+#include "segbatch.h"
 
 #pragma clang fp contract(off)
 
@@ -50,23 +51,12 @@
 #define OB_LAUNCHES 25         // 2 fills + 11 kernels + 4 scans of 3
 #define OB_NPARAM 4
 
-extern "C" int mopa_scan_exclusive_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* total, void* ws, size_t ws_bytes, void* stream);
-extern "C" size_t mopa_scan_workspace_bytes(int64_t n);
-
 struct ObParams {
   double eps, eps2, cell, max_distance;                // cell: the side of a grid cell
   int min_samples, include_noise, C;
   int cls[OB_MAXC];
 };
 
-__device__ __forceinline__ int ob_segment(const int32_t* __restrict__ blk0, int B, int blk) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (blk0[mid] <= blk) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 __device__ __forceinline__ int ob_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ------------------------------------------------------------------------------------------ 1. class positions + block counts
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(OB_THREADS) void k_ob_bin(const float* __restrict__
   const int32_t* row0 = tab;
   const int32_t* blk0 = tab + B + 1;
   const int C = P.C;
-  const int s = ob_segment(blk0, B, blockIdx.x);
+  const int s = seg_of_block(blk0, B, blockIdx.x);
   const int n = row0[s + 1] - row0[s];
   const int lb = blockIdx.x - blk0[s];
   const int nb = blk0[s + 1] <= (int)gridDim.x ? blk0[s + 1] - blk0[s] : 0;      // a table that names blocks past the grid is refused
@@ -126,7 +116,7 @@ __global__ __launch_bounds__(OB_THREADS) void k_ob_order(const float* __restrict
   const int32_t* row0 = tab;
   const int32_t* blk0 = tab + B + 1;
   const int C = P.C;
-  const int s = ob_segment(blk0, B, blockIdx.x);
+  const int s = seg_of_block(blk0, B, blockIdx.x);
   const int n = row0[s + 1] - row0[s];
   const int lb = blockIdx.x - blk0[s];
   const int nb = blk0[s + 1] <= (int)gridDim.x ? blk0[s + 1] - blk0[s] : 0;

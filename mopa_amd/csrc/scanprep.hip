@@ -5,28 +5,23 @@
 // mopa/data/semantic_kitti/semantic_kitti_dataloader.py:583-585,632-676, mopa/data/collate.py:182-264,
 // mopa/data/utils/augmentation_3d.py:48-59, mopa/data/utils/refine_pseudo_labels.py:5-22).
 //
-// A fixed number of launches whatever B is: every kernel covers all segments of the call.  A segment is cut into blocks of
-// SP_ROWS rows; the host builds the block table (blk0[s] = first block of segment s), a block finds its segment from it.
-// Per-segment pointers and draws travel as kernel arguments (at most SP_MAXS segments per call; the binding splits larger
-// batches).  The arithmetic is k_vox_minmax / k_vox_coords / k_rotate_f32 of hash3d.hip, restated per segment: same bits.
+// A fixed number of launches whatever B is: every kernel covers all segments of the call, cut into blocks of SP_ROWS rows
+// (segbatch.h: the block table, the counts and their scan).  Per-segment pointers and draws travel as kernel arguments (at most
+// SP_MAXS segments per call; the binding splits larger batches).  The arithmetic is k_vox_minmax / k_vox_coords / k_rotate_f32 of hash3d.hip, restated per segment: same bits.
 // The rotated points are written once and read by every later pass.  No float atomics: min / max go through integer
 // atomics on the ordered bit pattern, counts and histograms are integers, the compaction is ordered -> deterministic.
 #include "common.h"
+#include "segbatch.h"
 
 #define SP_MAXS 64             // segments per call: 32 scans, each with an optional un-augmented copy
 #define SP_MAXB 32             // scans per call
 #define SP_ROWS 1024           // rows per block (256 threads x 4 tiles)
 #define SP_MAXC 32             // classes of the refinement (pseudo.hip PS_MAXC)
 
-extern "C" int mopa_scan_exclusive_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* total, void* ws, size_t ws_bytes, void* stream);
-extern "C" size_t mopa_scan_workspace_bytes(int64_t n);
-
 struct SpSeg {
   const float* src[SP_MAXS];        // (n, 3) float32: the rotated points (or the points as loaded)
   const uint8_t* keep_in[SP_MAXS];  // (n,) 0/1 or null: rows removed before the minimum is taken
-  int32_t n[SP_MAXS];
-  int32_t row0[SP_MAXS + 1];        // first row of the segment in the call's flat row numbering
-  int32_t blk0[SP_MAXS + 1];        // first block of the segment
+  SegTable<SP_MAXS> seg;
 };
 struct SpTr {
   double u[SP_MAXB][3];             // the translation's rand(3) draws (scans only; copies are never translated)
@@ -35,24 +30,18 @@ struct SpTr {
 struct SpRot {
   const float* src[SP_MAXB];
   float* dst[SP_MAXB];
-  int32_t n[SP_MAXB];
-  int32_t blk0[SP_MAXB + 1];
+  SegTable<SP_MAXB> seg;
   float r[SP_MAXB][9];
 };
 struct SpSide {
   const void* label[SP_MAXB];       // (n,) raw class ids or null
   const int64_t* img[SP_MAXB];      // (n, 2) or null
   const float* src[SP_MAXB];        // (n, 3) rotated points
-  int32_t row0[SP_MAXB + 1];
+  SegTable<SP_MAXB> seg;
 };
 
 __device__ __forceinline__ int sp_f2ord(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7FFFFFFF; }
 __device__ __forceinline__ float sp_ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
-__device__ __forceinline__ int sp_segment(const int32_t* blk0, int S, int blk) {
-  int s = 0;
-  while (s + 1 < S && blk0[s + 1] <= blk) ++s;
-  return s;
-}
 __device__ __forceinline__ int64_t sp_label(const void* p, int dtype, int64_t i) {
   switch (dtype) {
     case 0: return ((const uint8_t*)p)[i];
@@ -65,14 +54,14 @@ __device__ __forceinline__ int64_t sp_label(const void* p, int dtype, int64_t i)
 // ------------------------------------------------------------------------------------------ 1. rotation
 // out = points @ R per scan, float32 as fma(z, r2j, fma(y, r1j, x * r0j)) (k_rotate_f32).
 __global__ __launch_bounds__(256) void k_sp_rotate(const SpRot a, int S) {
-  const int s = sp_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s];
   const float* __restrict__ p = a.src[s];
   float* __restrict__ o = a.dst[s];
   float r[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) r[k] = a.r[s][k];
-  const int base = (blockIdx.x - a.blk0[s]) * SP_ROWS;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * SP_ROWS;
 #pragma unroll
   for (int t = 0; t < SP_ROWS / 256; ++t) {
     const int i = base + t * 256 + threadIdx.x;
@@ -90,11 +79,11 @@ __global__ void k_sp_init(int* __restrict__ mm, int S) {
 }
 __global__ __launch_bounds__(256) void k_sp_minmax(const SpSeg a, int S, float scale, int* __restrict__ mm) {
   __shared__ int red[4][6];
-  const int s = sp_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s];
   const float* __restrict__ p = a.src[s];
   const uint8_t* __restrict__ kin = a.keep_in[s];
-  const int base = (blockIdx.x - a.blk0[s]) * SP_ROWS;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * SP_ROWS;
   float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
   for (int t = 0; t < SP_ROWS / 256; ++t) {
@@ -160,14 +149,13 @@ __device__ __forceinline__ bool sp_coords(const float* __restrict__ p, int64_t i
 // cnt[blk] = emitted rows of the block, cnt[nblk + blk] = rows of the block that survive keep_in.
 __global__ __launch_bounds__(256) void k_sp_flags(const SpSeg a, const SpTr tr, int S, int B, float scale, int full_scale,
                                                   const int* __restrict__ mm, uint8_t* __restrict__ flags, int* __restrict__ cnt, int nblk) {
-  __shared__ int red[4][2];
-  const int s = sp_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s];
   const float* __restrict__ p = a.src[s];
   const uint8_t* __restrict__ kin = a.keep_in[s];
   const SpField f = sp_field(mm, s, B, tr, full_scale);
-  const int base = (blockIdx.x - a.blk0[s]) * SP_ROWS;
-  int c2 = 0, c1 = 0;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * SP_ROWS;
+  int c[2] = {0, 0};                // emitted rows, rows that survive keep_in
 #pragma unroll
   for (int t = 0; t < SP_ROWS / 256; ++t) {
     const int i = base + t * 256 + threadIdx.x;
@@ -175,40 +163,23 @@ __global__ __launch_bounds__(256) void k_sp_flags(const SpSeg a, const SpTr tr, 
       const bool k1 = !kin || kin[i];
       bool ok = false;
       if (k1) { int64_t ci[3]; ok = sp_coords(p, i, scale, full_scale, f, ci); }
-      flags[(int64_t)a.row0[s] + i] = (uint8_t)((ok ? 1 : 0) | ((kin && k1) ? 2 : 0));
-      c2 += ok;
-      c1 += k1;
+      flags[(int64_t)a.seg.row0[s] + i] = (uint8_t)((ok ? 1 : 0) | ((kin && k1) ? 2 : 0));
+      c[0] += ok;
+      c[1] += k1;
     }
   }
-  c2 = wave_sum_i(c2);
-  c1 = wave_sum_i(c1);
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = c2; red[threadIdx.x >> 6][1] = c1; }
-  __syncthreads();
-  if (threadIdx.x < 2) cnt[threadIdx.x * nblk + blockIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+  block_counts(c, cnt, nblk);
 }
 // offsets[s] = first output row of segment s (s <= S; the copies count from offsets[B] on), offsets[S + 1 + b] = first row of
 // scan b among the rows that survive keep_in (b <= B).  scan = exclusive scan of cnt.
 __global__ void k_sp_offsets(const SpSeg a, int S, int B, const int* __restrict__ scan, int nblk, int64_t* __restrict__ offsets) {
   const int i = threadIdx.x;   // blk0[S] = nblk, and the scan has one item more than counts: scan[2 nblk] is the grand total
-  if (i <= S) offsets[i] = scan[a.blk0[i]];
-  if (i <= B) offsets[S + 1 + i] = scan[nblk + a.blk0[i]] - scan[nblk];
+  if (i <= S) offsets[i] = scan[a.seg.blk0[i]];
+  if (i <= B) offsets[S + 1 + i] = scan[nblk + a.seg.blk0[i]] - scan[nblk];
 }
 
 // ------------------------------------------------------------------------------------------ 4. compaction
 struct __attribute__((aligned(32))) SpLoc { int64_t x, y, z, b; };
-__device__ __forceinline__ int sp_rank(bool p, int* lds, int& total) {
-  const unsigned long long m = __ballot(p);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = __popcll(m & ((1ull << lane) - 1ull));
-  if (lane == 0) lds[w] = __popcll(m);
-  __syncthreads();
-  int pre = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { const int c = lds[k]; pre += k < w ? c : 0; tot += c; }
-  __syncthreads();
-  total = tot;
-  return pre + r;
-}
 // identity != 0 (nothing is removed): row i of segment s goes to row0[s] + i, rows outside the field are counted in n_outside.
 // Otherwise the rows with flag bit 0 go, in order, to scan[blk] + rank; rows with bit 1 write their bit 0 to mask1 (the
 // reference's idxs of a cropped scan) and their point index to gather1.  locs / gather receive the scans, ori_locs the copies (segments >= B).
@@ -218,18 +189,18 @@ __global__ __launch_bounds__(256) void k_sp_compact(const SpSeg a, const SpTr tr
                                                     SpLoc* __restrict__ ori_locs, int64_t* __restrict__ gather, int64_t gather_base,
                                                     uint8_t* __restrict__ mask1, int64_t* __restrict__ gather1, int* __restrict__ n_outside) {
   __shared__ int lds[4];
-  const int s = sp_segment(a.blk0, S, blockIdx.x);
-  const int n = a.n[s];
+  const int s = seg_of_block(a.seg.blk0, S, blockIdx.x);
+  const int n = a.seg.n[s];
   const float* __restrict__ p = a.src[s];
   const SpField f = sp_field(mm, s, B, tr, full_scale);
-  const int base = (blockIdx.x - a.blk0[s]) * SP_ROWS;
+  const int base = (blockIdx.x - a.seg.blk0[s]) * SP_ROWS;
   const bool copy = s >= B;
   SpLoc* __restrict__ dst = copy ? ori_locs : locs;
   int64_t run2, run1 = 0;
   if (identity) {
-    run2 = (int64_t)a.row0[s] - (copy ? a.row0[B] : 0) + base;
+    run2 = (int64_t)a.seg.row0[s] - (copy ? a.seg.row0[B] : 0) + base;
   } else {
-    run2 = (int64_t)scan[blockIdx.x] - (copy ? scan[a.blk0[B]] : 0);
+    run2 = (int64_t)scan[blockIdx.x] - (copy ? scan[a.seg.blk0[B]] : 0);
     run1 = (int64_t)scan[nblk + blockIdx.x] - scan[nblk];
   }
   int outside = 0;
@@ -243,24 +214,24 @@ __global__ __launch_bounds__(256) void k_sp_compact(const SpSeg a, const SpTr tr
         outside += !sp_coords(p, i, scale, full_scale, f, ci);
         const int64_t o = run2 + t * 256 + threadIdx.x;
         dst[o] = SpLoc{ci[0], ci[1], ci[2], (int64_t)(batch0 + (copy ? s - B : s))};
-        if (!copy) gather[o] = gather_base + a.row0[s] + i;
+        if (!copy) gather[o] = gather_base + a.seg.row0[s] + i;
       }
       continue;
     }
-    const uint8_t fl = valid ? flags[(int64_t)a.row0[s] + i] : 0;
+    const uint8_t fl = valid ? flags[(int64_t)a.seg.row0[s] + i] : 0;
     int tot2, tot1 = 0;
-    const int r2 = sp_rank(fl & 1, lds, tot2);
+    const int r2 = block_rank<256>(fl & 1, lds, tot2);
     if (fl & 1) {
       int64_t ci[3];
       sp_coords(p, i, scale, full_scale, f, ci);
       dst[run2 + r2] = SpLoc{ci[0], ci[1], ci[2], (int64_t)(batch0 + (copy ? s - B : s))};
-      if (!copy) gather[run2 + r2] = gather_base + a.row0[s] + i;
+      if (!copy) gather[run2 + r2] = gather_base + a.seg.row0[s] + i;
     }
     run2 += tot2;
     if (mask1 && !copy) {
       const bool k1 = valid && (a.keep_in[s] ? (fl & 2) != 0 : true);
-      const int r1 = sp_rank(k1, lds, tot1);
-      if (k1) { mask1[run1 + r1] = fl & 1; gather1[run1 + r1] = gather_base + a.row0[s] + i; }
+      const int r1 = block_rank<256>(k1, lds, tot1);
+      if (k1) { mask1[run1 + r1] = fl & 1; gather1[run1 + r1] = gather_base + a.seg.row0[s] + i; }
       run1 += tot1;
     }
   }
@@ -279,7 +250,7 @@ __global__ __launch_bounds__(256) void k_sp_take(const SpSide a, int B, const in
                                                  int64_t* __restrict__ label_out, SpPair* __restrict__ img_out, float* __restrict__ pts_out,
                                                  int64_t* __restrict__ ps2_out, int64_t* __restrict__ ps3_out) {
   __shared__ int row0[SP_MAXB + 1];
-  if (threadIdx.x <= B) row0[threadIdx.x] = a.row0[threadIdx.x];
+  if (threadIdx.x <= B) row0[threadIdx.x] = a.seg.row0[threadIdx.x];
   __syncthreads();
   for (int64_t m = blockIdx.x * (int64_t)256 + threadIdx.x; m < M; m += (int64_t)gridDim.x * 256) {
     const int64_t g = gather ? gather[m] - gather_base : m;
@@ -304,32 +275,15 @@ __global__ __launch_bounds__(256) void k_sp_take(const SpSide a, int B, const in
   }
 }
 
-static int sp_blocks(const int32_t* n_host, int S, int32_t* blk0, int32_t* row0) {
-  int64_t blk = 0, row = 0;
-  for (int s = 0; s < S; ++s) {
-    if (n_host[s] < 0) return -1;
-    blk0[s] = (int32_t)blk;
-    if (row0) row0[s] = (int32_t)row;
-    blk += cdiv64(n_host[s], SP_ROWS);
-    row += n_host[s];
-    if (row >= (int64_t)1 << 30) return -1;
-  }
-  blk0[S] = (int32_t)blk;
-  if (row0) row0[S] = (int32_t)row;
-  return (int)blk;
-}
-
 MOPA_API int mopa_scanprep_rotate(const void* const* src_host, void* const* dst_host, const int32_t* n_host, const float* rot_host /*[S][9]*/,
                                   int32_t S, void* stream) {
-  if (!src_host || !dst_host || !n_host || !rot_host || S < 1 || S > SP_MAXB) return MOPA_ERR_ARG;
   SpRot a = {};
-  const int nblk = sp_blocks(n_host, S, a.blk0, nullptr);
-  if (nblk < 0) return MOPA_ERR_ARG;
+  const int nblk = seg_table_fill(a.seg, n_host, S, SP_ROWS);
+  if (nblk < 0 || !src_host || !dst_host || !rot_host) return MOPA_ERR_ARG;
   for (int s = 0; s < S; ++s) {
     if (n_host[s] > 0 && (!src_host[s] || !dst_host[s])) return MOPA_ERR_ARG;
     a.src[s] = (const float*)src_host[s];
     a.dst[s] = (float*)dst_host[s];
-    a.n[s] = n_host[s];
     for (int k = 0; k < 9; ++k) a.r[s][k] = rot_host[s * 9 + k];
   }
   if (nblk == 0) return MOPA_OK;
@@ -338,24 +292,22 @@ MOPA_API int mopa_scanprep_rotate(const void* const* src_host, void* const* dst_
   return MOPA_OK;
 }
 
-// workspace: mm [S][6] | cnt [2 nblk] | scan [2 nblk + 1] | total | scratch of the scan
-static size_t sp_ws_ints(int64_t nblk) { return (size_t)(SP_MAXS * 6 + 4 * nblk + 16); }
+// workspace: mm [SP_MAXS][6], then the two count planes (emitted, surviving keep_in) of segbatch.h's SegCounts
 MOPA_API size_t mopa_scanprep_workspace_bytes(int64_t total_blocks) {
   if (total_blocks < 0) return 0;
-  return align_up(sp_ws_ints(total_blocks) * sizeof(int), 256) + mopa_scan_workspace_bytes(2 * total_blocks + 1);
+  return seg_counts_bytes(2, total_blocks, SP_MAXS * 6);
 }
 MOPA_API int mopa_scanprep_rows_per_block(void) { return SP_ROWS; }
 
 static int sp_fill(SpSeg& a, SpTr& tr, const void* const* src_host, const void* const* keep_in_host, const int32_t* n_host,
                    const double* u_host, const int32_t* transl_host, int S, int B) {
-  if (!src_host || !n_host || S < 1 || S > SP_MAXS || B < 1 || B > SP_MAXB || (S != B && S != 2 * B)) return -1;
-  const int nblk = sp_blocks(n_host, S, a.blk0, a.row0);
+  if (!src_host || B < 1 || B > SP_MAXB || (S != B && S != 2 * B)) return -1;
+  const int nblk = seg_table_fill(a.seg, n_host, S, SP_ROWS);
   if (nblk < 0) return -1;
   for (int s = 0; s < S; ++s) {
     if (n_host[s] > 0 && !src_host[s]) return -1;
     a.src[s] = (const float*)src_host[s];
     a.keep_in[s] = keep_in_host ? (const uint8_t*)keep_in_host[s] : nullptr;
-    a.n[s] = n_host[s];
   }
   for (int b = 0; b < B; ++b) {
     tr.on[b] = transl_host && transl_host[b];
@@ -379,19 +331,14 @@ MOPA_API int mopa_scanprep_count(const void* const* src_host, const void* const*
   if (ws_bytes < mopa_scanprep_workspace_bytes(nblk)) return MOPA_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   int* mm = (int*)ws;
-  int* cnt = mm + SP_MAXS * 6;
-  int* scan = cnt + 2 * nblk;
-  int* tot = scan + 2 * nblk + 1;
-  void* sws = (char*)ws + align_up(sp_ws_ints(nblk) * sizeof(int), 256);
+  const SegCounts c = seg_counts(ws, 2, nblk, SP_MAXS * 6);
   k_sp_init<<<1, 256, 0, st>>>(mm, S);
   if (nblk > 0) k_sp_minmax<<<nblk, 256, 0, st>>>(a, S, scale, mm);
   if (count) {
-    if (nblk > 0) k_sp_flags<<<nblk, 256, 0, st>>>(a, tr, S, B, scale, full_scale, mm, flags, cnt, nblk);
-    // one more (zero) item so that scan[2 nblk] exists for every lookup; its value is never counted
-    if (hipMemsetAsync(cnt + 2 * nblk, 0, sizeof(int), st) != hipSuccess) return MOPA_ERR_LAUNCH;
-    const int rc = mopa_scan_exclusive_i32(cnt, scan, 2 * nblk + 1, tot, sws, mopa_scan_workspace_bytes(2 * nblk + 1), stream);
+    if (nblk > 0) k_sp_flags<<<nblk, 256, 0, st>>>(a, tr, S, B, scale, full_scale, mm, flags, c.cnt, nblk);
+    const int rc = seg_counts_scan(c, stream);
     if (rc) return rc;
-    k_sp_offsets<<<1, 128, 0, st>>>(a, S, B, scan, nblk, offsets);
+    k_sp_offsets<<<1, 128, 0, st>>>(a, S, B, c.scan, nblk, offsets);
   }
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
@@ -412,8 +359,8 @@ MOPA_API int mopa_scanprep_compact(const void* const* src_host, const void* cons
   if ((((uintptr_t)locs | (uintptr_t)ori_locs) & 31)) return MOPA_ERR_ARG;
   if (ws_bytes < mopa_scanprep_workspace_bytes(nblk)) return MOPA_ERR_WORKSPACE;
   if (nblk == 0) return MOPA_OK;
-  int* mm = (int*)ws;
-  int* scan = mm + SP_MAXS * 6 + 2 * nblk;
+  const int* mm = (const int*)ws;
+  const int* scan = seg_counts(ws, 2, nblk, SP_MAXS * 6).scan;
   k_sp_compact<<<nblk, 256, 0, (hipStream_t)stream>>>(a, tr, S, B, batch0, scale, full_scale, identity, mm, flags, scan, nblk, (SpLoc*)locs,
                                                       (SpLoc*)ori_locs, gather, gather_base, mask1, gather1, n_outside);
   MOPA_CHECK_LAUNCH();
@@ -428,14 +375,13 @@ MOPA_API int mopa_scanprep_take(const int64_t* gather, int64_t gather_base, int6
                                 int64_t ignore_label, const void* const* img_host, const void* const* src_host, const int64_t* ps2,
                                 const int64_t* ps3, int64_t* label_out, int64_t* img_out, float* pts_out, int64_t* ps2_out,
                                 int64_t* ps3_out, void* stream) {
-  if (!n_host || B < 1 || B > SP_MAXB || M < 0 || label_dtype < 0 || label_dtype > 3 || (label_map && map_len <= 0)) return MOPA_ERR_ARG;
+  if (M < 0 || label_dtype < 0 || label_dtype > 3 || (label_map && map_len <= 0)) return MOPA_ERR_ARG;
   if ((label_out && !label_host) || (img_out && !img_host) || (pts_out && !src_host) || (ps2_out && !ps2) || (ps3_out && !ps3))
     return MOPA_ERR_ARG;
   if (((uintptr_t)img_out & 15)) return MOPA_ERR_ARG;
   SpSide a = {};
-  int32_t blk0[SP_MAXB + 1];
-  if (sp_blocks(n_host, B, blk0, a.row0) < 0) return MOPA_ERR_ARG;
-  if (!gather && M != a.row0[B]) return MOPA_ERR_ARG;
+  if (seg_table_fill(a.seg, n_host, B, SP_ROWS) < 0) return MOPA_ERR_ARG;
+  if (!gather && M != a.seg.row0[B]) return MOPA_ERR_ARG;
   for (int b = 0; b < B; ++b) {
     a.label[b] = label_host ? label_host[b] : nullptr;
     a.img[b] = img_host ? (const int64_t*)img_host[b] : nullptr;

@@ -18,11 +18,13 @@ differently; the fixture's generator asserts the equality and fails where it doe
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
 
 from ._lib import call, chunk_ranges, host_addr, host_i32, host_ptrs, ptr, query, stream
+from ._prep import check_devices, ground_mask, image_size_wh, out_rows, read_counts, tensor_checker
 
 _NAME = "prepare_scans_kitti"
 _PSEUDO = ("ori_keep_idx", "ori_img_points")
@@ -34,12 +36,7 @@ def _check(samples, image_size):
     """Types, dtypes and shapes first (so that a malformed call is named as such on any device), then the device."""
     if not samples:
         raise ValueError(f"{_NAME}: no samples")
-    try:
-        w, h = (int(v) for v in image_size)
-    except (TypeError, ValueError):
-        raise ValueError(f"{_NAME}: image_size must be (W, H), got {image_size!r}") from None
-    if w <= 0 or h <= 0 or w >= 1 << 24 or h >= 1 << 24:
-        raise ValueError(f"{_NAME}: image_size must be (W, H) with positive sides, got {image_size!r}")
+    w, h = image_size_wh(_NAME, image_size)
     for key in _OPTIONAL:
         have = [s.get(key) is not None for s in samples]
         if any(have) and not all(have):
@@ -48,17 +45,7 @@ def _check(samples, image_size):
     if (first.get("ori_keep_idx") is None) != (first.get("ori_img_points") is None):
         raise ValueError(f"{_NAME}: `ori_keep_idx` and `ori_img_points` come together")
     pseudo = first.get("ori_keep_idx") is not None
-    tensors = []
-
-    def tensor(b, s, key, dtypes, what):
-        t = s.get(key)
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{_NAME}: {key} of sample {b} must be a torch tensor on the GPU, got {type(t).__name__}")
-        if t.dtype not in dtypes:
-            raise TypeError(f"{_NAME}: {key} must be {what}, got {t.dtype}")
-        tensors.append((key, t))
-        return t
-
+    tensor, tensors = tensor_checker(_NAME)
     for b, s in enumerate(samples):
         scan = tensor(b, s, "scan", (torch.float32,), "float32")
         if scan.dim() != 2 or scan.shape[1] != 4:
@@ -86,11 +73,7 @@ def _check(samples, image_size):
             p = tensor(b, s, "ori_img_points", (torch.float32,), "float32")
             if p.dim() != 2 or p.shape[1] != 2:
                 raise ValueError(f"{_NAME}: ori_img_points of sample {b} must be (Nk, 2), got {tuple(p.shape)}")
-    for key, t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{_NAME}: {key} must be on the GPU (there is no CPU fallback)")
-        if t.device != tensors[0][1].device:
-            raise ValueError(f"{_NAME}: {key} is on {t.device}; all tensors of a call must be on one device")
+    check_devices(_NAME, tensors)
     return w, h, pseudo
 
 
@@ -142,25 +125,13 @@ def prepare_scans_kitti(samples, image_size, with_full: bool = False) -> dict:
             m = np.stack([samples[b]["proj_matrix"].astype(np.float32) for b in range(s, e)]).reshape(-1)
             c["proj"] = (ctypes.c_float * (12 * Bc))(*m.tolist())
         if has_g:
-            g = [samples[b]["g_indices"].contiguous() for b in range(s, e)]
-            c["gmask"] = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-            c["bad"] = torch.empty(1, dtype=torch.int32, device=dev)
-            gt, gn = host_ptrs(g), host_i32([t.numel() for t in g])
-            call("mopa_kittiprep_ground", host_addr(gt), host_addr(gn), host_addr(c["n"]), Bc, ptr(c["gmask"]), ptr(c["bad"]), stream())
+            c["gmask"], c["bad"] = ground_mask(call, [samples[b]["g_indices"] for b in range(s, e)], c["n"])
         call("mopa_kittiprep_count", host_addr(c["scan"]), host_addr(c["n"]), host_addr(c["proj"]), host_addr(mask_t), host_addr(mask_n),
              Bc, w, h, ptr(c["flags"]), ptr(c["bad"]), ptr(c["counts"]), ptr(c["ws"]), c["ws"].numel(), stream())
         chunks.append(c)
 
     # the one read-back: per chunk [Nz, Nk] of every scan, then the number of ground indices outside their scan
-    dev_counts = chunks[0]["counts"] if len(chunks) == 1 else torch.cat([c["counts"] for c in chunks])
-    host = dev_counts.cpu().numpy()
-    counts = np.zeros((B, 2), dtype=np.int64)
-    at = 0
-    for c in chunks:
-        counts[c["s"]:c["e"]] = host[at:at + 2 * c["B"]].reshape(-1, 2)
-        if host[at + 2 * c["B"]]:
-            raise IndexError(f"{_NAME}: g_indices of samples {c['s']}..{c['e'] - 1} hold {int(host[at + 2 * c['B']])} indices outside their scan")
-        at += 2 * c["B"] + 1
+    counts = read_counts(_NAME, chunks, 2)
     nz, nk = [int(v) for v in counts[:, 0]], [int(v) for v in counts[:, 1]]
     if pseudo:
         for b, s in enumerate(samples):
@@ -170,10 +141,7 @@ def prepare_scans_kitti(samples, image_size, with_full: bool = False) -> dict:
                 raise ValueError(f"{_NAME}: ori_img_points of sample {b} has {s['ori_img_points'].shape[0]} rows, ori_keep_idx keeps {nk[b]} points")
     Z, K = sum(nz), sum(nk)
 
-    def _rows(n, *shape, dtype=torch.float32):                # (tensor, bytes per row, address): never a null address, also when every row was dropped
-        t = torch.empty(max(n, 1), *shape, dtype=dtype, device=dev)
-        return t[:n], t.stride(0) * t.element_size(), t.data_ptr()
-
+    _rows = functools.partial(out_rows, device=dev)
     none = (None, 0, None)
     out = {"points": _rows(K, 3), "feats": _rows(K, 1), "seg": _rows(K, dtype=torch.int16), "img": none if pseudo else _rows(K, 2),
            "keep": _rows(Z, dtype=torch.uint8), "g": _rows(K, dtype=torch.uint8) if has_g else none,

@@ -18,10 +18,13 @@ nuscenes-devkit, which were not at hand: UNVERIFIED against the libraries themse
 """
 from __future__ import annotations
 
+import functools
+
 import numpy as np
 import torch
 
 from ._lib import call, chunk_ranges, host_addr, host_i32, host_ptrs, ptr, query, stream
+from ._prep import check_devices, ground_mask, image_size_wh, out_rows, read_counts, tensor_checker
 
 _NAME = "prepare_scans_nuscenes"
 CALIB_KEYS = ("lidar2ego_rotation", "ego2global_rotation_lidar", "ego2global_rotation_cam", "cam2ego_rotation",
@@ -71,12 +74,7 @@ def _check(samples, image_size, with_ground):
     -> (W, H, ground form: None / "g_indices" / "g_mask", per sample (calib (37,), boxes (M, 11)))."""
     if not samples:
         raise ValueError(f"{_NAME}: no samples")
-    try:
-        w, h = (int(v) for v in image_size)
-    except (TypeError, ValueError):
-        raise ValueError(f"{_NAME}: image_size must be (W, H), got {image_size!r}") from None
-    if w <= 0 or h <= 0 or w >= 1 << 24 or h >= 1 << 24:
-        raise ValueError(f"{_NAME}: image_size must be (W, H) with positive sides, got {image_size!r}")
+    w, h = image_size_wh(_NAME, image_size)
     for s in samples:
         if not isinstance(s, dict):
             raise TypeError(f"{_NAME}: every sample must be a dict, got {type(s).__name__}")
@@ -92,16 +90,8 @@ def _check(samples, image_size, with_ground):
         raise ValueError(f"{_NAME}: with_ground needs `g_indices` or `g_mask` in every sample")
     if with_ground is not None and not with_ground:
         form = None
-    tensors, host = [], []
-
-    def tensor(b, s, key, dtypes, what):
-        t = s.get(key)
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{_NAME}: {key} of sample {b} must be a torch tensor on the GPU, got {type(t).__name__}")
-        if t.dtype not in dtypes:
-            raise TypeError(f"{_NAME}: {key} must be {what}, got {t.dtype}")
-        tensors.append((key, t))
-        return t
+    host = []
+    tensor, tensors = tensor_checker(_NAME)
 
     def array(b, what, v, shape):
         if isinstance(v, torch.Tensor):
@@ -165,11 +155,7 @@ def _check(samples, image_size, with_ground):
             g = tensor(b, s, "g_mask", (torch.bool,), "bool")
             if tuple(g.shape) != (n,):
                 raise ValueError(f"{_NAME}: g_mask of sample {b} must be ({n},) for {n} points, got {tuple(g.shape)}")
-    for key, t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError(f"{_NAME}: {key} must be on the GPU (there is no CPU fallback)")
-        if t.device != tensors[0][1].device:
-            raise ValueError(f"{_NAME}: {key} is on {t.device}; all tensors of a call must be on one device")
+    check_devices(_NAME, tensors)
     return w, h, form, host
 
 
@@ -218,11 +204,7 @@ def prepare_scans_nuscenes(samples, image_size=(1600, 900), with_ground=None) ->
         c["counts"] = torch.empty(Bc + 1, dtype=torch.int64, device=dev)
         call("mopa_nuscprep_setup", ptr(c["in"]), ptr(c["in"], 37 * Bc) if M else None, Bc, M, ptr(c["table"]), stream())
         if form == "g_indices":
-            g = [samples[b]["g_indices"].contiguous() for b in range(s, e)]
-            c["gmask"] = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-            c["bad"] = torch.empty(1, dtype=torch.int32, device=dev)
-            gt, gn = host_ptrs(g), host_i32([t.numel() for t in g])
-            call("mopa_kittiprep_ground", host_addr(gt), host_addr(gn), host_addr(c["n"]), Bc, ptr(c["gmask"]), ptr(c["bad"]), stream())
+            c["gmask"], c["bad"] = ground_mask(call, [samples[b]["g_indices"] for b in range(s, e)], c["n"])
         elif form == "g_mask":
             c["gmask"] = torch.cat([samples[b]["g_mask"].reshape(-1) for b in range(s, e)] + [torch.zeros(1, dtype=torch.bool, device=dev)]).view(torch.uint8)
         call("mopa_nuscprep_count", host_addr(c["scan"]), host_addr(c["n"]), host_addr(c["cols"]), Bc, ptr(c["table"]), w, h,
@@ -231,22 +213,11 @@ def prepare_scans_nuscenes(samples, image_size=(1600, 900), with_ground=None) ->
         r0 += total
 
     # the one read-back: per chunk Nk of every scan, then the number of ground indices outside their scan
-    dev_counts = chunks[0]["counts"] if len(chunks) == 1 else torch.cat([c["counts"] for c in chunks])
-    got = dev_counts.cpu().numpy()
-    counts = np.zeros(B, dtype=np.int64)
-    at = 0
-    for c in chunks:
-        counts[c["s"]:c["e"]] = got[at:at + c["B"]]
-        if got[at + c["B"]]:
-            raise IndexError(f"{_NAME}: g_indices of samples {c['s']}..{c['e'] - 1} hold {int(got[at + c['B']])} indices outside their scan")
-        at += c["B"] + 1
+    counts = read_counts(_NAME, chunks, 1).reshape(-1)
     nk = [int(v) for v in counts]
     K = sum(nk)
 
-    def _rows(*shape, dtype=torch.float32):                   # never a null address, also when every row was dropped
-        t = torch.empty(max(K, 1), *shape, dtype=dtype, device=dev)
-        return t[:K], t.stride(0) * t.element_size(), t.data_ptr()
-
+    _rows = functools.partial(out_rows, K, device=dev)
     out = {"points": _rows(3), "img": _rows(2), "seg": _rows(dtype=torch.uint8), "g": _rows(dtype=torch.uint8) if form else (None, 0, None)}
     k0 = 0
     for c in chunks:

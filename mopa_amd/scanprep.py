@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import call, chunk_ranges, host_addr, host_i32, host_ptrs, ptr, query, stream, workspace
+from ._prep import out_rows
 from .voxelize import draw_rotation
 
 MAXB = 32                       # csrc/scanprep.hip SP_MAXB: scans per launch
@@ -264,9 +265,9 @@ def prepare_batch_3d(samples, scale, full_scale: int = 4096, label_mapping=None,
     M, K, Mo = sum(counts), sum(kcounts), sum(ocounts)
 
     # 4. compaction
-    def _rows(n, *shape, dtype=torch.int64):               # (address, tensor): never a null address, also when every row was dropped
-        t = torch.empty(max(n, 1), *shape, dtype=dtype, device=dev)
-        return t.data_ptr(), t[:n]
+    def _rows(n, *shape, dtype=torch.int64):               # (address, tensor)
+        t, _, addr = out_rows(n, *shape, dtype=dtype, device=dev)
+        return addr, t
 
     (locs_p, locs), (gather_p, gather) = _rows(M, 4), _rows(M)
     ori_p, ori_locs = _rows(Mo, 4) if ema_input else (None, None)

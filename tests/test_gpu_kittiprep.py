@@ -148,6 +148,29 @@ def test_int64_labels_and_single_samples_give_the_same_rows(g13):
             assert equal(res[key][0], g[f"c{k}_s{b}_{key}"]), (key, b)
 
 
+def test_an_empty_last_scan_changes_nothing_before_it(g13):
+    """A call whose LAST scan is empty: the block table ends with two equal entries (the empty scan owns no block).  One block
+    and one row of a second block, 300 rows, no rows -- each scan gives what it gives alone."""
+    from mopa_amd import _lib
+    from mopa_amd.kittiprep import prepare_scans_kitti
+    g, meta = g13
+    k = [c["name"] for c in meta["cases"]].index("sizes")
+    case = meta["cases"][k]
+    five = device_samples(g, k, case)
+    rows = _lib.query("mopa_kittiprep_rows_per_block")
+    assert [s["scan"].shape[0] for s in five][:4] == [2 * rows + 3, 0, 1, 300]
+    cut = dict(five[0], scan=five[0]["scan"][:rows + 1], label=five[0]["label"][:rows + 1])
+    samples = [{key: s[key] for key in ("scan", "label", "proj_matrix")} for s in (cut, five[3], five[1])]
+    together = prepare_scans_kitti(samples, tuple(case["image_size"]), with_full=True)
+    assert together["counts"][2].tolist() == [0, 0] and together["counts"][0, 0] > 0 and together["counts"][1, 0] > 0
+    for b, s in enumerate(samples):
+        alone = prepare_scans_kitti([s], tuple(case["image_size"]), with_full=True)
+        assert alone["counts"].tolist() == [together["counts"][b].tolist()]
+        for key in LISTS:
+            if key != "g_indices":
+                assert equal(together[key][b], alone[key][0].cpu()), (key, b)
+
+
 def test_more_scans_than_one_launch_takes(g13):
     """34 scans (the library takes 32 per launch): the call splits them, still with one read-back, same rows."""
     from mopa_amd import kittiprep
