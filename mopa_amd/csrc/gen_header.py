@@ -123,6 +123,16 @@ SECTIONS = [
  * accurate integer inverse DCT ("islow") into uint8 component tiles in LDS, then libjpeg-turbo's "fancy" chroma upsampling, YCbCr ->
  * RGB in 16-bit fixed point and the store into (H, W, 3) uint8 rows with a pitch; no workspace.  The chain is stated in DESIGN.md section 4; yardstick
  * tests/_jpeg_reference.py, held against Pillow 12.2 (libjpeg-turbo) bit for bit."""),
+    ("pngdec.hip", """PNG decoding split at the filtered scanlines -- np.asarray(Image.open(path)) of SemanticKITTI's image_2 frames and of
+ * A2D2's camera and label images (mopa/data/semantic_kitti/semantic_kitti_dataloader.py:563-566, mopa/data/a2d2/preprocess.py:96-141),
+ * Pillow's bits after convert("RGB").  Host half (mopa_amd/pngdec.py, no GPU needed): chunk walk with CRC32, IHDR / PLTE / IDAT /
+ * IEND, inflate through the standard library's zlib capped one byte past H * (1 + stride); 8-bit samples, colour types 0 / 2 / 3 /
+ * 4 / 6, non-interlaced, sides up to 8192.  Device half, all images of a call in one launch (at most 32 images per call), one
+ * workgroup per image: lane = row, the rows of a pass advance as a wavefront with a skew of one pixel (the pixel above by lane
+ * shuffle, between waves and passes through LDS), None / Sub / Up / Average / Paeth undone on the bytes of a pixel side by side, and
+ * the expansion to RGB (grey replicated, alpha dropped, palette looked up) in the store into (H, W, 3) uint8 rows with a pitch;
+ * integer only, no atomics, no workspace, no workgroup waits for another.  The chain is stated in DESIGN.md section 4; yardstick
+ * tests/_png_reference.py, held against Pillow 12.2."""),
     ("ground.hip", """Ground estimation on the device, all scans of an iteration per launch: the per-point ground mask that obj_on_road
  * (mopa/data/mixmatch_ss.py:380-388) gets from Patchwork++ on the host and the shipped configs load from g_indices_dir
  * (the preprocess.py of each dataset under mopa/data).  NOT the bits of Patchwork++: the published Patchwork core stated in DESIGN.md section 4 (504 patches
