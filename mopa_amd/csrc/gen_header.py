@@ -56,6 +56,16 @@ SECTIONS = [
     ("losses.hip", """Losses: cross-modal KL (mopa/train/train_xmuda_mopa.py:389-398,440-445), weighted CE with ignore_index -100
  * (:354-363,456-465,563-567), softmax over classes (:473) and mask_cons_loss (mopa/common/utils/loss.py:241-283).
  * Loss scalars, normalisers and upstream gradients are device pointers (no host sync)."""),
+    ("coral.hip", """logCORAL loss on the device: logcoral_loss of mopa/models/losses.py:47-93 (TRAIN.XMUDA.lambda_logcoral), float64 arithmetic
+ * on float32 features of width 1 <= F <= 64.  Forward: column means and centred Gram matrices of both inputs (a fixed number of
+ * blocks walk the rows; float64 partial slabs summed in index order), cov = Gram / (batch_size - 1) for BOTH inputs with
+ * batch_size = x_src.shape[0] before flattening, the reference's guard (an entry > 1e30 or NaN in either covariance turns both into
+ * the identity), a parallel cyclic two-sided Jacobi eigendecomposition in LDS (one workgroup per matrix, bounded sweeps),
+ * L = V diag(log|lambda|) V^T, loss = mean((L_src - L_trg)^2), and per input S = factor (dC + dC^T) from the divided-difference form of
+ * the matrix logarithm's derivative, kept with the means in `state`.  Backward: dX = g (x - mean) S per row, exact zeros under the
+ * guard.  No floating-point atomics: the same bits on every run.  `status` (int32 on the device, never read back by the call): bit 0 the
+ * guard fired, bit 1 Jacobi hit its sweep bound, bit 2 an eigenvalue was <= 0.  The arithmetic is stated in DESIGN.md section 4;
+ * yardstick tests/_coral_reference.py, held against the reference's float64 autograd."""),
     ("pseudo.hip", """Pseudo-label update of the MoPA phase on the device (SURVEY 8f-3): EMA teacher (torch_ema update rule,
  * mopa/train/train_xmuda_mopa.py:221-226,587-591), entropy-weighted 2D/3D fusion (:282-291 with mopa/models/losses.py:10-19)
  * and the per-class median refinement (mopa/data/utils/refine_pseudo_labels.py:5-22), without host round trips."""),
