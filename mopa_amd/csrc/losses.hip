@@ -158,29 +158,26 @@ MOPA_API int mopa_wce_bwd(const float* logits, const int64_t* labels, const floa
 }
 
 // ------------------------------------------------------------------------------------------ per-point training losses
-// The loss-and-metric block between the forward and backward passes of one domain half (train_xmuda_mopa.py:353-418,
-// :437-469,:563-576) in ONE row pass over the per-point logits of both networks: the two weighted CE values, the two
-// cross-modal KL values, SegIoU's two confusion matrices and pc_mm_acc's two counts.  Partition, accumulation order and the
-// CE / KL expressions are those of k_wce_partial / k_kl_partial / k_wce_finalize / k_scalar_finalize above, so every scalar
-// has the bits of the single entry point; the integers go through per-block LDS counters flushed with integer atomics, like
-// k_eval_logits (evaluate.hip).  The backward is one launch per network, as the reference backpropagates the two networks'
-// loss sums separately.
-#define PL_NPART 6   // per-block partials: CE numerator, CE normaliser, KL sum of the 2D network, then of the 3D network
+// The loss-and-metric block between the forward and backward passes (train_xmuda_mopa.py:353-418,:437-469,:563-576) in ONE row
+// pass over the per-point logits of both networks: the two weighted CE values, the two cross-modal KL values, SegIoU's two
+// confusion matrices and pc_mm_acc's two counts -- for every row segment of a MERGED pass (source, target and the VGI batch as
+// row segments of one logit tensor per network; bn_groups / bn_group_points upstream) in one forward launch pair and one backward
+// launch per network, with entropy minimisation (mopa/models/losses.py:21-34 on the softmax of the main head,
+// train_xmuda.py:323-330) as a third per-segment term.  A network's rows are the concatenation, in segment order, of the segments
+// it takes part in.  The FORWARD has one kernel set: the one-call entry point (mopa_point_losses_fwd, one domain half) runs it
+// over a table of one segment.  The backward has two kernels: k_point_losses_bwd (one call, its pointers `__restrict__` kernel
+// parameters, 59 VGPRs) is 1.35x faster on one segment than k_point_losses_seg_bwd (49 VGPRs), which reads its pointers from the
+// table (profiles/r33_trainloss_one_body.md).
+//
+// A block serves exactly one segment of n_s rows: g_s = stream_grid(n_s, 256) virtual blocks, partials [S][PL_SEG_TERMS][g_s].
+// Partition, accumulation order and the CE / KL expressions are those of k_wce_partial / k_kl_partial / k_wce_finalize /
+// k_scalar_finalize above on the segment's rows, so every CE / KL scalar and every gradient row without an entropy part has the
+// bits of the single entry point (tests/test_gpu_trainloss.py, test_gpu_trainloss_merged.py); the integers go through per-block
+// LDS counters flushed with integer atomics, like k_eval_logits (evaluate.hip).  The backward is one launch per network, as the
+// reference backpropagates the two networks' loss sums separately.
 #define PL_MAXGRID 2048
-
-struct PointLossArgs {
-  const float* zm[2];        // (N, C) main-head logits of the 2D / 3D network, or null
-  const float* zx[2];        // (N, C) logits of the head the KL term trains (== zm without a dual head), or null: no KL
-  const int64_t* y[2];       // (N,) labels, or null: no CE and no confusion matrix
-  const float* w;            // (C,) class weights or null
-  int64_t ignore;
-  int N, C;
-  int64_t* conf[2];          // (C, C) int64, rows = label, ADDED to; or null
-  const uint8_t* acc_mask;   // (N,) or null
-  int64_t* acc_out;          // [2]: #(mask && argmax(zm[1]) == y[1]), #mask; ADDED to
-  double* partial;           // [PL_NPART][gridDim.x]
-  int* status;
-};
+#define PL_MAXSEG 8
+#define PL_SEG_TERMS 8   // per-block partials of a segment: CE numerator, CE normaliser, KL sum, entropy sum of the 2D, then the 3D network
 
 // first maximal index; a NaN wins (torch.argmax, ev_row_stat of evaluate.hip)
 __device__ __forceinline__ int row_argmax(const float* __restrict__ z, int C) {
@@ -203,105 +200,6 @@ __device__ __forceinline__ float kl_row(const float* __restrict__ ar, float la, 
   return t;
 }
 
-__global__ __launch_bounds__(LOSS_BLOCK) void k_point_losses(PointLossArgs a) {
-  extern __shared__ int pl_hist[];   // [#matrices][C][C]
-  __shared__ double lds[8];
-  __shared__ int pl_acc[2];
-  const int C = a.C, CC = C * C;
-  int* hist[2] = {a.conf[0] ? pl_hist : nullptr, a.conf[1] ? pl_hist + (a.conf[0] ? CC : 0) : nullptr};
-  const int nh = ((a.conf[0] ? 1 : 0) + (a.conf[1] ? 1 : 0)) * CC;
-  for (int b = threadIdx.x; b < nh; b += blockDim.x) pl_hist[b] = 0;
-  if (threadIdx.x < 2) pl_acc[threadIdx.x] = 0;
-  __syncthreads();
-  const bool ce[2] = {a.zm[0] && a.y[0], a.zm[1] && a.y[1]};
-  const bool kl[2] = {a.zx[0] && a.zm[1], a.zx[1] && a.zm[0]};   // the target of a network's KL is the other's main head
-
-  double num[2] = {0.0, 0.0}, den[2] = {0.0, 0.0}, ksum[2] = {0.0, 0.0};
-  int hit = 0, seen = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.N; i += gridDim.x * blockDim.x) {
-    int64_t yi[2] = {0, 0};
-    bool keep[2] = {false, false};
-    float lm[2] = {0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (ce[k]) {
-        yi[k] = a.y[k][i];
-        if (yi[k] != a.ignore) {
-          if (yi[k] < 0 || yi[k] >= C) atomicOr(a.status, 1);
-          else keep[k] = true;
-        }
-      }
-      if (keep[k] || kl[1 - k] || (kl[k] && a.zx[k] == a.zm[k])) lm[k] = row_lse(a.zm[k] + (int64_t)i * C, C);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float* zr = a.zm[k] + (int64_t)i * C;
-      if (keep[k]) {
-        const float wi = a.w ? a.w[yi[k]] : 1.f;
-        num[k] += (double)(wi * (lm[k] - zr[yi[k]]));
-        den[k] += (double)wi;
-      }
-      if (kl[k]) {
-        const float* ar = a.zx[k] + (int64_t)i * C;
-        const float la = a.zx[k] == a.zm[k] ? lm[k] : row_lse(ar, C);
-        ksum[k] += (double)kl_row(ar, la, a.zm[1 - k] + (int64_t)i * C, lm[1 - k], C);
-      }
-      const bool masked = k == 1 && a.acc_mask && a.acc_mask[i];
-      if ((hist[k] && keep[k]) || masked) {
-        const int arg = row_argmax(zr, C);
-        if (hist[k] && keep[k]) atomicAdd(&hist[k][(int)yi[k] * C + arg], 1);
-        if (masked) { seen += 1; hit += (int64_t)arg == yi[k] ? 1 : 0; }
-      }
-    }
-  }
-  if (a.acc_mask) {
-    hit = wave_sum_i(hit);
-    seen = wave_sum_i(seen);
-    if ((threadIdx.x & 63) == 0 && seen) { atomicAdd(&pl_acc[0], hit); atomicAdd(&pl_acc[1], seen); }
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b < nh; b += blockDim.x) {
-    int64_t* dst = b < CC && a.conf[0] ? a.conf[0] + b : a.conf[1] + (b - (a.conf[0] ? CC : 0));
-    if (pl_hist[b]) atomicAdd(reinterpret_cast<unsigned long long*>(dst), (unsigned long long)pl_hist[b]);
-  }
-  if (a.acc_mask && threadIdx.x < 2 && pl_acc[threadIdx.x])
-    atomicAdd(reinterpret_cast<unsigned long long*>(a.acc_out + threadIdx.x), (unsigned long long)pl_acc[threadIdx.x]);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (ce[k]) {
-      const double sn = block_sum_d(num[k], lds);
-      const double sd = block_sum_d(den[k], lds);
-      if (threadIdx.x == 0) { a.partial[(3 * k) * gridDim.x + blockIdx.x] = sn; a.partial[(3 * k + 1) * gridDim.x + blockIdx.x] = sd; }
-    }
-    if (kl[k]) {
-      const double s = block_sum_d(ksum[k], lds);
-      if (threadIdx.x == 0) a.partial[(3 * k + 2) * gridDim.x + blockIdx.x] = s;
-    }
-  }
-}
-
-// One block; has: bit 0 / 1 = CE / KL of the 2D network, bit 2 / 3 of the 3D network.  scalars: ce, den, kl per network.
-__global__ void k_point_losses_finalize(const double* __restrict__ partial, int n, int has, double scale, float* __restrict__ scalars) {
-  __shared__ double lds[8];
-  for (int k = 0; k < 2; ++k) {
-    if (has >> (2 * k) & 1) {
-      const double* p = partial + (size_t)(3 * k) * n;
-      double a = 0.0, b = 0.0;
-      for (int i = threadIdx.x; i < n; i += blockDim.x) { a += p[i]; b += p[n + i]; }
-      const double sn = block_sum_d(a, lds);
-      const double sd = block_sum_d(b, lds);
-      if (threadIdx.x == 0) { scalars[3 * k] = (float)(sn / sd); scalars[3 * k + 1] = (float)sd; }
-    }
-    if (has >> (2 * k + 1) & 1) {
-      const double* p = partial + (size_t)(3 * k + 2) * n;
-      double acc = 0.0;
-      for (int i = threadIdx.x; i < n; i += blockDim.x) acc += p[i];
-      const double s = block_sum_d(acc, lds);
-      if (threadIdx.x == 0) scalars[3 * k + 2] = (float)(s * scale);
-    }
-  }
-}
-
 // The sum of a row's CE and KL gradient parts on a shared head: one rounding of the two finished parts, as a tensor add of
 // k_wce_bwd's and k_kl_bwd's results gives -- neither part's multiply may be contracted into this add.  The add is written
 // out under the pragma: __fadd_rn is a plain `x + y` in the HIP headers, compiled with THEIR contraction setting, and was fused
@@ -311,118 +209,6 @@ __device__ __forceinline__ float add_parts(float ce_part, float kl_part) {
   return ce_part + kl_part;
 }
 
-// One network's gradients: dz_main = d(g[0] ce)/dz_main (k_wce_bwd's expression), dz_xm = d(g[1] kl)/dz_xm (k_kl_bwd's);
-// on a shared head (z_xm == z_main, dz_xm == dz_main) the sum of the two.
-__global__ __launch_bounds__(LOSS_BLOCK) void k_point_losses_bwd(const float* __restrict__ z_main, const float* __restrict__ z_xm,
-                                                                  const float* __restrict__ z_other, const int64_t* __restrict__ y,
-                                                                  const float* __restrict__ w, int N, int C, int64_t ignore,
-                                                                  const float* __restrict__ den, const float* __restrict__ g,
-                                                                  float* dz_main, float* dz_xm) {
-  const bool ce = y != nullptr, kl = z_other != nullptr, shared = kl && z_xm == z_main;
-  const float gce = ce ? g[0] / *den : 0.f;
-  const float gkl = kl ? g[1] / (float)N : 0.f;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
-    int64_t yi = 0;
-    bool keep = false;
-    if (ce) {
-      yi = y[i];
-      keep = !(yi == ignore || yi < 0 || yi >= C);
-    }
-    const float* zr = z_main + (int64_t)i * C;
-    float l = 0.f, s = 0.f;
-    if (keep) {
-      l = row_lse(zr, C);
-      s = gce * (w ? w[yi] : 1.f);
-    }
-    if (shared) {
-      const float* br = z_other + (int64_t)i * C;
-      const float la = keep ? l : row_lse(zr, C), lb = row_lse(br, C);
-      float* d = dz_main + (int64_t)i * C;
-      for (int c = 0; c < C; ++c) {
-        const float pk = gkl * (expf(zr[c] - la) - expf(br[c] - lb));
-        if (ce) d[c] = add_parts(keep ? s * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f)) : 0.f, pk);
-        else d[c] = pk;
-      }
-      continue;
-    }
-    if (ce) {
-      float* d = dz_main + (int64_t)i * C;
-      if (keep) for (int c = 0; c < C; ++c) d[c] = s * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f));
-      else for (int c = 0; c < C; ++c) d[c] = 0.f;
-    }
-    if (kl) {
-      const float* ar = z_xm + (int64_t)i * C;
-      const float* br = z_other + (int64_t)i * C;
-      const float la = row_lse(ar, C), lb = row_lse(br, C);
-      for (int c = 0; c < C; ++c) dz_xm[(int64_t)i * C + c] = gkl * (expf(ar[c] - la) - expf(br[c] - lb));
-    }
-  }
-}
-
-MOPA_API size_t mopa_point_losses_workspace_bytes(int64_t n_rows) { return align_up((size_t)PL_NPART * PL_MAXGRID * sizeof(double), 256); }
-
-// z*_main / z*_xm (N, C) fp32 contiguous; a network's KL term exists when its z*_xm and the OTHER network's z*_main are given
-// (z*_xm may equal z*_main: no dual head), its CE term and confusion matrix when its z*_main and y are.  y2 / y3 (N,) int64,
-// may be the same pointer.  class_weight (C,) or null.  scalars fp32[8]: ce_2d, den_2d, kl_2d, ce_3d, den_3d, kl_3d, two spare;
-// the entries of absent terms are left untouched.  conf_2d / conf_3d (C, C) int64, rows = label, ADDED to, nullable.
-// acc_mask (N,) uint8 nullable with acc_out int64[2], ADDED to: #(mask && argmax(z3_main) == y3), #mask.
-// status: device int, bit0 set when a label is outside [0,C) and != ignore (as mopa_wce_fwd).
-MOPA_API int mopa_point_losses_fwd(const float* z2_main, const float* z2_xm, const float* z3_main, const float* z3_xm,
-                                   const int64_t* y2, const int64_t* y3, const float* class_weight, int32_t N, int32_t C,
-                                   int64_t ignore_index, float* scalars, int64_t* conf_2d, int64_t* conf_3d,
-                                   const uint8_t* acc_mask, int64_t* acc_out, int32_t* status, void* ws, size_t ws_bytes,
-                                   void* stream) {
-  if (N <= 0 || C <= 0 || C > MAXC || !scalars) return MOPA_ERR_ARG;
-  if ((y2 && !z2_main) || (y3 && !z3_main) || ((y2 || y3) && !status)) return MOPA_ERR_ARG;
-  if ((conf_2d && !y2) || (conf_3d && !y3)) return MOPA_ERR_ARG;
-  if (acc_mask && (!y3 || !acc_out)) return MOPA_ERR_ARG;
-  const int has = (y2 ? 1 : 0) | (z2_xm && z3_main ? 2 : 0) | (y3 ? 4 : 0) | (z3_xm && z2_main ? 8 : 0);
-  if (!has) return MOPA_ERR_ARG;
-  if (ws_bytes < mopa_point_losses_workspace_bytes(N)) return MOPA_ERR_WORKSPACE;
-  PointLossArgs a;
-  a.zm[0] = z2_main; a.zm[1] = z3_main; a.zx[0] = z2_xm; a.zx[1] = z3_xm;
-  a.y[0] = y2; a.y[1] = y3; a.w = class_weight; a.ignore = ignore_index;
-  a.N = N; a.C = C;
-  a.conf[0] = conf_2d; a.conf[1] = conf_3d;
-  a.acc_mask = acc_mask; a.acc_out = acc_out;
-  a.partial = (double*)ws; a.status = status;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = stream_grid(N, LOSS_BLOCK);   // <= PL_MAXGRID
-  const size_t lds = (size_t)((conf_2d ? 1 : 0) + (conf_3d ? 1 : 0)) * C * C * sizeof(int);   // <= 32 KB at MAXC
-  k_point_losses<<<g, LOSS_BLOCK, lds, st>>>(a);
-  k_point_losses_finalize<<<1, 256, 0, st>>>((const double*)ws, g, has, 1.0 / N, scalars);
-  MOPA_CHECK_LAUNCH();
-  return MOPA_OK;
-}
-
-// One network's backward.  y null: no CE part; z_other_main (the detached KL target) null: no KL part.  den: the network's
-// normaliser in `scalars`; g fp32[2]: upstream gradients of (ce, kl).  z_xm == z_main (shared head) needs dz_xm == dz_main,
-// which then receives the sum of the two parts; otherwise dz_main gets the CE part and dz_xm the KL part.
-MOPA_API int mopa_point_losses_bwd(const float* z_main, const float* z_xm, const float* z_other_main, const int64_t* y,
-                                   const float* class_weight, int32_t N, int32_t C, int64_t ignore_index, const float* den,
-                                   const float* g, float* dz_main, float* dz_xm, void* stream) {
-  if (N <= 0 || C <= 0 || C > MAXC || !g) return MOPA_ERR_ARG;
-  if (!y && !z_other_main) return MOPA_ERR_ARG;
-  if (y && (!z_main || !den || !dz_main)) return MOPA_ERR_ARG;
-  if (z_other_main && (!z_xm || !dz_xm)) return MOPA_ERR_ARG;
-  if (z_xm && (z_xm == z_main) != (dz_xm == dz_main)) return MOPA_ERR_ARG;
-  k_point_losses_bwd<<<stream_grid(N, LOSS_BLOCK), LOSS_BLOCK, 0, (hipStream_t)stream>>>(
-      z_main, z_xm, z_other_main, y, class_weight, N, C, ignore_index, den, g, dz_main, dz_xm);
-  MOPA_CHECK_LAUNCH();
-  return MOPA_OK;
-}
-
-// ------------------------------------------------------------------------------------------ the same block over row segments
-// The loss block of a MERGED pass (source, target and the VGI batch as row segments of one logit tensor per network; bn_groups /
-// bn_group_points upstream): all segments of an iteration in one forward launch pair and one backward launch per network, and
-// entropy minimisation (mopa/models/losses.py:21-34 on the softmax of the main head, train_xmuda.py:323-330) as a third
-// per-segment term.  A block serves exactly one segment and reduces it as k_point_losses reduces a call of N = n_s rows:
-// g_s = stream_grid(n_s, 256) virtual blocks, the same row walk, the same device functions and block_sum_d order, partials
-// [S][PL_SEG_TERMS][g_s] -- so every CE / KL scalar and every gradient row without an entropy part has the bits of the
-// per-slice call (tests/test_gpu_trainloss_merged.py).  A network's rows are the concatenation, in segment order, of the segments
-// it takes part in.
-#define PL_MAXSEG 8
-#define PL_SEG_TERMS 8   // per-block partials of a segment: CE numerator, CE normaliser, KL sum, entropy sum of the 2D, then the 3D network
 #define PL_SEG_KL 1
 #define PL_SEG_WEIGHTED 2
 #define PL_SEG_MINENT 4
@@ -582,37 +368,38 @@ struct PointLossSegFin {
   double kl_scale[PL_MAXSEG];    // 1 / n_s
   double ent_scale[PL_MAXSEG];   // -1 / (n_s log2 C)
   const double* partial;
-  float* scalars;            // [S][2][4]: ce, den, kl, ent
+  float* scalars;            // [S][2][stride]: ce, den, kl, ent
+  int stride;                // 4; 3 in the one-call layout, which has no entropy term
 };
 
-// One block per segment: k_point_losses_finalize's sums over the segment's g_s partials.
+// One block per segment: k_wce_finalize's / k_scalar_finalize's sums over the segment's g_s partials.
 __global__ void k_point_losses_seg_finalize(PointLossSegFin f) {
   __shared__ double lds[8];
   const int s = blockIdx.x, n = f.blk0[s + 1] - f.blk0[s], has = f.has[s];
   const double* base = f.partial + (size_t)PL_SEG_TERMS * f.blk0[s];
-  float* out = f.scalars + 8 * s;
   for (int k = 0; k < 2; ++k) {
+    float* out = f.scalars + (2 * s + k) * f.stride;
     if (has >> (4 * k) & 1) {
       const double* p = base + (size_t)(4 * k) * n;
       double a = 0.0, b = 0.0;
       for (int i = threadIdx.x; i < n; i += blockDim.x) { a += p[i]; b += p[n + i]; }
       const double sn = block_sum_d(a, lds);
       const double sd = block_sum_d(b, lds);
-      if (threadIdx.x == 0) { out[4 * k] = (float)(sn / sd); out[4 * k + 1] = (float)sd; }
+      if (threadIdx.x == 0) { out[0] = (float)(sn / sd); out[1] = (float)sd; }
     }
     if (has >> (4 * k + 1) & 1) {
       const double* p = base + (size_t)(4 * k + 2) * n;
       double acc = 0.0;
       for (int i = threadIdx.x; i < n; i += blockDim.x) acc += p[i];
       const double sk = block_sum_d(acc, lds);
-      if (threadIdx.x == 0) out[4 * k + 2] = (float)(sk * f.kl_scale[s]);
+      if (threadIdx.x == 0) out[2] = (float)(sk * f.kl_scale[s]);
     }
     if (has >> (4 * k + 2) & 1) {
       const double* p = base + (size_t)(4 * k + 3) * n;
       double acc = 0.0;
       for (int i = threadIdx.x; i < n; i += blockDim.x) acc += p[i];
       const double se = block_sum_d(acc, lds);
-      if (threadIdx.x == 0) out[4 * k + 3] = (float)(se * f.ent_scale[s]);
+      if (threadIdx.x == 0) out[3] = (float)(se * f.ent_scale[s]);
     }
   }
 }
@@ -738,6 +525,48 @@ static bool seg_rows_ok(const PointLossSeg* sg, int S, int k, const float* z, in
   return at == (z ? n_rows : 0);
 }
 
+// The terms of one segment (PointLossSegFin::has): per network a CE term where labels are given, a KL term with flag 1 where both
+// networks take part and the network's KL head is given, an entropy term with flag 4 where the network takes part.
+static int seg_terms(const PointLossSeg& d, const float* const* zx) {
+  int has = 0;
+  for (int k = 0; k < 2; ++k) {
+    if (d.y[k]) has |= 1 << (4 * k);
+    if ((d.flags & PL_SEG_KL) && d.row0[0] >= 0 && d.row0[1] >= 0 && zx[k]) has |= 2 << (4 * k);
+    if ((d.flags & PL_SEG_MINENT) && d.row0[k] >= 0) has |= 4 << (4 * k);
+  }
+  return has;
+}
+
+// The forward launch pair over a table its entry point has checked; `stride` floats of `scalars` per network.
+static int launch_point_losses(const float* const* zm, const float* const* zx, const float* w, const PointLossSeg* sg, int S, int C,
+                               int64_t ignore, float* scalars, int stride, int32_t* status, void* ws, void* stream) {
+  PointLossSegArgs a;
+  PointLossSegFin f;
+  int grid = 0;
+  size_t lds = 0;
+  for (int s = 0; s < S; ++s) {
+    const PointLossSeg& d = sg[s];
+    a.seg[s] = d;
+    a.blk0[s] = f.blk0[s] = grid;
+    grid += d.n > 0 ? stream_grid(d.n, LOSS_BLOCK) : 0;   // <= PL_MAXGRID each
+    f.has[s] = seg_terms(d, zx);
+    f.kl_scale[s] = 1.0 / (double)d.n;                    // n = 0: inf, and 0 * inf = NaN as .mean() of nothing
+    f.ent_scale[s] = -1.0 / ((double)d.n * log2((double)C));
+    const size_t need = (size_t)((d.conf[0] ? 1 : 0) + (d.conf[1] ? 1 : 0)) * C * C * sizeof(int);   // <= 32 KB at MAXC
+    lds = need > lds ? need : lds;
+  }
+  for (int s = S; s <= PL_MAXSEG; ++s) a.blk0[s] = f.blk0[s] = grid;
+  a.zm[0] = zm[0]; a.zm[1] = zm[1]; a.zx[0] = zx[0]; a.zx[1] = zx[1];
+  a.w = w; a.ignore = ignore; a.S = S; a.C = C;
+  a.partial = (double*)ws; a.status = status;
+  f.partial = (const double*)ws; f.scalars = scalars; f.stride = stride;
+  hipStream_t st = (hipStream_t)stream;
+  if (grid) k_point_losses_seg<<<grid, LOSS_BLOCK, lds, st>>>(a);
+  k_point_losses_seg_finalize<<<S, 256, 0, st>>>(f);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
 // The loss-and-metric block of all row segments of a merged pass.  z*_main / z*_xm (N2 | N3, C) fp32 contiguous, as in
 // mopa_point_losses_fwd (z*_xm null: that network has no KL term).  segs_host: S <= 8 descriptors of ten int64 each --
 // n, row0_2d, row0_3d (-1: the network takes no part), y_2d, y_3d, acc_mask, conf_2d, conf_3d, acc_out (device pointers,
@@ -752,49 +581,23 @@ MOPA_API int mopa_point_losses_seg_fwd(const float* z2_main, const float* z2_xm,
   if ((z2_xm && !z2_main) || (z3_xm && !z3_main)) return MOPA_ERR_ARG;
   const PointLossSeg* sg = reinterpret_cast<const PointLossSeg*>(segs_host);
   if (!seg_rows_ok(sg, S, 0, z2_main, N2) || !seg_rows_ok(sg, S, 1, z3_main, N3)) return MOPA_ERR_ARG;
-  PointLossSegArgs a;
-  PointLossSegFin f;
+  const float* zm[2] = {z2_main, z3_main};
   const float* zx[2] = {z2_xm, z3_xm};
-  int any = 0, grid = 0;
-  size_t lds = 0;
+  int any = 0;
   for (int s = 0; s < S; ++s) {
     const PointLossSeg& d = sg[s];
-    const int flags = (int)d.flags;
     if (d.flags & ~(int64_t)(PL_SEG_KL | PL_SEG_WEIGHTED | PL_SEG_MINENT)) return MOPA_ERR_ARG;
-    if ((flags & PL_SEG_MINENT) && C < 2) return MOPA_ERR_ARG;   // the reference divides by log2(1)
-    int has = 0, mats = 0;
+    if ((d.flags & PL_SEG_MINENT) && C < 2) return MOPA_ERR_ARG;   // the reference divides by log2(1)
     for (int k = 0; k < 2; ++k) {
-      const bool in = d.row0[k] >= 0;
-      if (d.y[k] && (!in || !status)) return MOPA_ERR_ARG;
+      if (d.y[k] && (d.row0[k] < 0 || !status)) return MOPA_ERR_ARG;
       if (d.conf[k] && !d.y[k]) return MOPA_ERR_ARG;
-      mats += d.conf[k] ? 1 : 0;
-      if (d.y[k]) has |= 1 << (4 * k);
-      if ((flags & PL_SEG_KL) && d.row0[0] >= 0 && d.row0[1] >= 0 && zx[k]) has |= 2 << (4 * k);
-      if ((flags & PL_SEG_MINENT) && in) has |= 4 << (4 * k);
     }
     if (d.acc_mask && (!d.y[1] || !d.acc_out)) return MOPA_ERR_ARG;
-    any |= has;
-    a.seg[s] = d;
-    a.blk0[s] = f.blk0[s] = grid;
-    grid += d.n > 0 ? stream_grid(d.n, LOSS_BLOCK) : 0;   // <= PL_MAXGRID each
-    f.has[s] = has;
-    f.kl_scale[s] = 1.0 / (double)d.n;                    // n = 0: inf, and 0 * inf = NaN as .mean() of nothing
-    f.ent_scale[s] = -1.0 / ((double)d.n * log2((double)C));
-    const size_t need = (size_t)mats * C * C * sizeof(int);   // <= 32 KB at MAXC
-    lds = need > lds ? need : lds;
+    any |= seg_terms(d, zx);
   }
   if (!any) return MOPA_ERR_ARG;
   if (ws_bytes < mopa_point_losses_seg_workspace_bytes(S)) return MOPA_ERR_WORKSPACE;
-  for (int s = S; s <= PL_MAXSEG; ++s) a.blk0[s] = f.blk0[s] = grid;
-  a.zm[0] = z2_main; a.zm[1] = z3_main; a.zx[0] = z2_xm; a.zx[1] = z3_xm;
-  a.w = class_weight; a.ignore = ignore_index; a.S = S; a.C = C;
-  a.partial = (double*)ws; a.status = status;
-  f.partial = (const double*)ws; f.scalars = scalars;
-  hipStream_t st = (hipStream_t)stream;
-  if (grid) k_point_losses_seg<<<grid, LOSS_BLOCK, lds, st>>>(a);
-  k_point_losses_seg_finalize<<<S, 256, 0, st>>>(f);
-  MOPA_CHECK_LAUNCH();
-  return MOPA_OK;
+  return launch_point_losses(zm, zx, class_weight, sg, S, C, ignore_index, scalars, 4, status, ws, stream);
 }
 
 // One network's backward over all of its N rows (net 0: the 2D network, 1: the 3D network), the same table.  z_main (N, C) and
@@ -829,6 +632,107 @@ MOPA_API int mopa_point_losses_seg_bwd(int32_t net, const float* z_main, const f
   a.S = S; a.C = C; a.net = net; a.log2c = log2f((float)C);
   a.scalars = scalars; a.g = g; a.dz_main = dz_main; a.dz_xm = dz_xm;
   if (grid) k_point_losses_seg_bwd<<<grid, LOSS_BLOCK, 0, (hipStream_t)stream>>>(a);
+  MOPA_CHECK_LAUNCH();
+  return MOPA_OK;
+}
+
+// ------------------------------------------------------------------------------------------ ... and over one domain half
+// The one-call form.  Forward: one segment of N rows that both networks (where given) take part in, through the segment
+// kernels, in its own memory layout (scalars at 3 floats per network).  Backward: a kernel of its own, see above.
+MOPA_API size_t mopa_point_losses_workspace_bytes(int64_t n_rows) { return mopa_point_losses_seg_workspace_bytes(1); }
+
+// z*_main / z*_xm (N, C) fp32 contiguous; a network's KL term exists when its z*_xm and the OTHER network's z*_main are given
+// (z*_xm may equal z*_main: no dual head), its CE term and confusion matrix when its z*_main and y are.  y2 / y3 (N,) int64,
+// may be the same pointer.  class_weight (C,) or null.  scalars fp32[8]: ce_2d, den_2d, kl_2d, ce_3d, den_3d, kl_3d, two spare;
+// the entries of absent terms are left untouched.  conf_2d / conf_3d (C, C) int64, rows = label, ADDED to, nullable.
+// acc_mask (N,) uint8 nullable with acc_out int64[2], ADDED to: #(mask && argmax(z3_main) == y3), #mask.
+// status: device int, bit0 set when a label is outside [0,C) and != ignore (as mopa_wce_fwd).
+MOPA_API int mopa_point_losses_fwd(const float* z2_main, const float* z2_xm, const float* z3_main, const float* z3_xm,
+                                   const int64_t* y2, const int64_t* y3, const float* class_weight, int32_t N, int32_t C,
+                                   int64_t ignore_index, float* scalars, int64_t* conf_2d, int64_t* conf_3d,
+                                   const uint8_t* acc_mask, int64_t* acc_out, int32_t* status, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  if (N <= 0 || C <= 0 || C > MAXC || !scalars) return MOPA_ERR_ARG;
+  if ((y2 && !z2_main) || (y3 && !z3_main) || ((y2 || y3) && !status)) return MOPA_ERR_ARG;
+  if ((conf_2d && !y2) || (conf_3d && !y3)) return MOPA_ERR_ARG;
+  if (acc_mask && (!y3 || !acc_out)) return MOPA_ERR_ARG;
+  const int has = (y2 ? 1 : 0) | (z2_xm && z3_main ? 2 : 0) | (y3 ? 4 : 0) | (z3_xm && z2_main ? 8 : 0);
+  if (!has) return MOPA_ERR_ARG;
+  if (ws_bytes < mopa_point_losses_workspace_bytes(N)) return MOPA_ERR_WORKSPACE;
+  const float* zm[2] = {z2_main, z3_main};
+  const float* zx[2] = {z2_xm, z3_xm};
+  for (int k = 0; k < 2; ++k)   // a KL head given without its own main head: it takes the main head's place, the other's KL has no target
+    if (!zm[k] && zx[k] && zm[1 - k]) { zm[k] = zx[k]; zx[1 - k] = nullptr; }
+  PointLossSeg d = {};
+  d.n = N;
+  d.row0[0] = zm[0] ? 0 : -1; d.row0[1] = zm[1] ? 0 : -1;
+  d.y[0] = y2; d.y[1] = y3; d.acc_mask = acc_mask;
+  d.conf[0] = conf_2d; d.conf[1] = conf_3d; d.acc_out = acc_out;
+  d.flags = ((has & 10) ? PL_SEG_KL : 0) | (class_weight ? PL_SEG_WEIGHTED : 0);
+  return launch_point_losses(zm, zx, class_weight, &d, 1, C, ignore_index, scalars, 3, status, ws, stream);
+}
+
+// One network's gradients: dz_main = d(g[0] ce)/dz_main (k_wce_bwd's expression), dz_xm = d(g[1] kl)/dz_xm (k_kl_bwd's);
+// on a shared head (z_xm == z_main, dz_xm == dz_main) the sum of the two.
+__global__ __launch_bounds__(LOSS_BLOCK) void k_point_losses_bwd(const float* __restrict__ z_main, const float* __restrict__ z_xm,
+                                                                  const float* __restrict__ z_other, const int64_t* __restrict__ y,
+                                                                  const float* __restrict__ w, int N, int C, int64_t ignore,
+                                                                  const float* __restrict__ den, const float* __restrict__ g,
+                                                                  float* dz_main, float* dz_xm) {
+  const bool ce = y != nullptr, kl = z_other != nullptr, shared = kl && z_xm == z_main;
+  const float gce = ce ? g[0] / *den : 0.f;
+  const float gkl = kl ? g[1] / (float)N : 0.f;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
+    int64_t yi = 0;
+    bool keep = false;
+    if (ce) {
+      yi = y[i];
+      keep = !(yi == ignore || yi < 0 || yi >= C);
+    }
+    const float* zr = z_main + (int64_t)i * C;
+    float l = 0.f, s = 0.f;
+    if (keep) {
+      l = row_lse(zr, C);
+      s = gce * (w ? w[yi] : 1.f);
+    }
+    if (shared) {
+      const float* br = z_other + (int64_t)i * C;
+      const float la = keep ? l : row_lse(zr, C), lb = row_lse(br, C);
+      float* d = dz_main + (int64_t)i * C;
+      for (int c = 0; c < C; ++c) {
+        const float pk = gkl * (expf(zr[c] - la) - expf(br[c] - lb));
+        if (ce) d[c] = add_parts(keep ? s * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f)) : 0.f, pk);
+        else d[c] = pk;
+      }
+      continue;
+    }
+    if (ce) {
+      float* d = dz_main + (int64_t)i * C;
+      if (keep) for (int c = 0; c < C; ++c) d[c] = s * (expf(zr[c] - l) - (c == yi ? 1.f : 0.f));
+      else for (int c = 0; c < C; ++c) d[c] = 0.f;
+    }
+    if (kl) {
+      const float* ar = z_xm + (int64_t)i * C;
+      const float* br = z_other + (int64_t)i * C;
+      const float la = row_lse(ar, C), lb = row_lse(br, C);
+      for (int c = 0; c < C; ++c) dz_xm[(int64_t)i * C + c] = gkl * (expf(ar[c] - la) - expf(br[c] - lb));
+    }
+  }
+}
+
+// One network's backward.  y null: no CE part; z_other_main (the detached KL target) null: no KL part.  den: the network's
+// normaliser in `scalars`; g fp32[2]: upstream gradients of (ce, kl).  z_xm == z_main (shared head) needs dz_xm == dz_main,
+// which then receives the sum of the two parts; otherwise dz_main gets the CE part and dz_xm the KL part.
+MOPA_API int mopa_point_losses_bwd(const float* z_main, const float* z_xm, const float* z_other_main, const int64_t* y,
+                                   const float* class_weight, int32_t N, int32_t C, int64_t ignore_index, const float* den,
+                                   const float* g, float* dz_main, float* dz_xm, void* stream) {
+  if (N <= 0 || C <= 0 || C > MAXC || !g) return MOPA_ERR_ARG;
+  if (!y && !z_other_main) return MOPA_ERR_ARG;
+  if (y && (!z_main || !den || !dz_main)) return MOPA_ERR_ARG;
+  if (z_other_main && (!z_xm || !dz_xm)) return MOPA_ERR_ARG;
+  if (z_xm && (z_xm == z_main) != (dz_xm == dz_main)) return MOPA_ERR_ARG;
+  k_point_losses_bwd<<<stream_grid(N, LOSS_BLOCK), LOSS_BLOCK, 0, (hipStream_t)stream>>>(
+      z_main, z_xm, z_other_main, y, class_weight, N, C, ignore_index, den, g, dz_main, dz_xm);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }

@@ -4,7 +4,9 @@
 ``:437-469`` (target) and ``:563-576`` (the VGI batch): the two ``F.cross_entropy`` calls, the two cross-modal ``F.kl_div`` calls,
 the two ``SegIoU.update_dict`` calls and ``pc_mm_acc`` -- one forward launch pair for everything, one backward launch per network,
 and no host read (``seg_ce`` x2 + ``xm_kl`` x2 are 8 forward and 4 backward launches, ``update_dict`` syncs the host twice per call).
-Every scalar and every gradient has the bits ``seg_ce`` / ``xm_kl`` give on the same tensors.
+Every scalar and every gradient has the bits ``seg_ce`` / ``xm_kl`` give on the same tensors.  The forward of mopa_point_losses_fwd is the
+one-segment form of the merged block's kernels (one forward kernel set; its workspace is mopa_point_losses_seg_workspace_bytes(1));
+the backward keeps a kernel of its own, which is faster on one segment (profiles/r33_trainloss_one_body.md).
 
 The two networks keep separate autograd nodes, as the reference backpropagates ``sum(loss_2d)`` and ``sum(loss_3d)`` separately:
 a node takes its own network's logits only, the other network's enter detached (see ``xm_kl``).

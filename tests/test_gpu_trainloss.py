@@ -194,6 +194,22 @@ def test_degenerate_forms():
     assert _same_bits(sc[2:3], _kl(z2x, z3m)) and _same_bits(sc[5:6], _kl(z3x, z2m))
 
 
+@pytest.mark.parametrize("N,C", ((257, 5), (4099, 10)))
+def test_forward_kl_head_given_without_its_main_head(N, C):
+    """z*_main null with z*_xm given: that network's KL term exists (its target, the other network's main head, is there) and has the
+    bits of mopa_softmax_kl_fwd; the other network's KL term has no target and is absent, its CE term is as ever."""
+    d = _dev(N, C)
+    y, w = d["y"], d["w"]
+    sc, status = _fwd(None, d["z2x"], d["z3m"], d["z3x"], None, y, w, N, C)
+    assert _same_bits(sc[2:3], _kl(d["z2x"], d["z3m"])) and _same_bits(sc[3:5], _ce(d["z3m"], y, w)[0])
+    assert (sc[[0, 1, 5, 6, 7]] == SENTINEL).all() and status.item() == 0
+    sc, status = _fwd(d["z2m"], d["z2x"], None, d["z3x"], y, None, w, N, C)
+    assert _same_bits(sc[5:6], _kl(d["z3x"], d["z2m"])) and _same_bits(sc[0:2], _ce(d["z2m"], y, w)[0])
+    assert (sc[[2, 3, 4, 6, 7]] == SENTINEL).all() and status.item() == 0
+    sc, _ = _fwd(None, d["z2x"], d["z3m"], None, None, None, None, N, C)     # that KL term alone
+    assert _same_bits(sc[2:3], _kl(d["z2x"], d["z3m"])) and (sc[[0, 1, 3, 4, 5, 6, 7]] == SENTINEL).all()
+
+
 def test_all_labels_of_one_network_ignored():
     N, C = 1000, 11
     d = _dev(N, C)

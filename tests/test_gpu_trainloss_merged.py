@@ -726,3 +726,11 @@ def test_refused_calls_write_nothing():
     bwd(C, lib.ptr(z[0]), lib.ptr(o["dz"][0]))
     torch.cuda.synchronize()
     assert (o["dz"][0] != SENTINEL).all() and (o["dz"][1] == SENTINEL).all()
+
+
+def test_one_call_workspace_is_one_segments():
+    """mopa_point_losses_fwd runs the segment kernels over one segment: its workspace is that segment's, whatever N."""
+    lib = _lib()
+    one = lib.query("mopa_point_losses_seg_workspace_bytes", 1)
+    for N in (1, 524588):
+        assert lib.query("mopa_point_losses_workspace_bytes", N) == one
