@@ -158,3 +158,149 @@ def mask_cons_loss(all_logits: torch.Tensor, sam_mask_ls: List[torch.Tensor], mi
     if masks.shape[0] != all_logits.shape[0] or masks.numel() * all_logits.shape[-1] != all_logits.numel():
         raise RuntimeError(f"mask_cons_loss: probs {tuple(all_logits.shape)} vs masks {tuple(masks.shape)}")
     return _MaskCons.apply(all_logits, masks, bool(min_entropy))
+
+
+# ------------------------------------------------------------------------------------------------ Lovasz-softmax (csrc/lovasz.hip)
+LOVASZ_MAX_CLASSES = 64    # csrc/lovasz.hip: the selected classes of a segment are the bits of one word
+LOVASZ_MAX_SEGMENTS = 32
+
+
+def _lovasz_classes(classes, C):
+    """-> (class_mode, class_mask) of mopa_lovasz_fwd."""
+    if isinstance(classes, str):
+        if classes not in ("present", "all"):
+            raise ValueError(f"lovasz_softmax: classes must be 'present', 'all' or a list of classes, not {classes!r}")
+        return (0 if classes == "present" else 1), 0
+    mask = 0
+    for c in classes:
+        c = int(c)
+        if not 0 <= c < C:
+            raise ValueError(f"lovasz_softmax: class {c} of the list is outside [0, {C})")
+        mask |= 1 << c
+    return 2, mask
+
+
+class _Lovasz(torch.autograd.Function):
+    """loss (0-d float32) of contiguous float32 (P, C) probabilities or logits; backward = one mopa_lovasz_bwd launch."""
+
+    @staticmethod
+    def forward(ctx, x, labels, from_logits, offsets, ignore, mode, mask, aux):
+        import ctypes
+        P, C = x.shape
+        dev = x.device
+        S = len(offsets) - 1
+        off = (ctypes.c_int64 * (S + 1))(*offsets)
+        has_ignore = ignore is not None
+        ign = int(ignore) if has_ignore else 0
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        coef = torch.empty((P, C), dtype=torch.float64 if from_logits else torch.float32, device=dev)
+        lse = torch.empty(P, dtype=torch.float32, device=dev) if from_logits else None
+        state = torch.empty(query("mopa_lovasz_state_bytes") // 8, dtype=torch.float64, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = workspace.get(query("mopa_lovasz_workspace_bytes", P, C, S), dev)
+        call("mopa_lovasz_fwd", ptr(x), int(from_logits), ptr(labels), P, C, ctypes.addressof(off), S, ign, int(has_ignore), mode, mask,
+             ptr(loss), ptr(coef), ptr(lse), ptr(state), ptr(status), ptr(ws), ws.numel(), stream())
+        ctx.save_for_backward(x, labels, coef, state)
+        ctx.lse, ctx.args = lse, (bool(from_logits), tuple(offsets), ign, int(has_ignore))
+        aux["state"], aux["status"] = state, status
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        x, labels, coef, state = ctx.saved_tensors
+        from_logits, offsets, ign, has_ignore = ctx.args
+        P, C = x.shape
+        S = len(offsets) - 1
+        off = (ctypes.c_int64 * (S + 1))(*offsets)
+        dx = torch.empty_like(x)
+        call("mopa_lovasz_bwd", ptr(coef), int(from_logits), ptr(x), ptr(ctx.lse), ptr(labels), P, C, ctypes.addressof(off), S, ign,
+             has_ignore, ptr(state), ptr(_f32c(g)), ptr(dx), stream())
+        return dx, None, None, None, None, None, None, None
+
+
+def _lovasz_call(name, x2d, labels, from_logits, offsets, ignore, classes):
+    """x2d (P, C), labels (P,): checks, then the autograd node; the result carries .loss64 and .status."""
+    P, C = x2d.shape
+    if C == 1:
+        raise ValueError(f"{name}: C == 1 (the reference's sigmoid branch) is not supported; the class dimension needs 2..64 entries")
+    if not 2 <= C <= LOVASZ_MAX_CLASSES:
+        raise ValueError(f"{name}: {C} classes are outside 2..{LOVASZ_MAX_CLASSES}")
+    if labels.numel() != P:
+        raise ValueError(f"{name}: {labels.numel()} labels for {P} rows of {tuple(x2d.shape)}")
+    if not x2d.is_floating_point() or labels.is_floating_point():
+        raise ValueError(f"{name}: floating-point probabilities and integer labels are expected")
+    S = len(offsets) - 1
+    if not 1 <= S <= LOVASZ_MAX_SEGMENTS:
+        raise ValueError(f"{name}: {S} row segments are outside 1..{LOVASZ_MAX_SEGMENTS}")
+    if offsets[0] != 0 or offsets[-1] != P or any(b < a for a, b in zip(offsets[:-1], offsets[1:])):
+        raise ValueError(f"{name}: the segment offsets {list(offsets)} must rise from 0 to {P}")
+    mode, mask = _lovasz_classes(classes, C)
+    if not x2d.is_cuda:
+        raise RuntimeError(f"{name}: the input is a CPU tensor; the hot path has no CPU fallback")
+    if P == 0:   # nothing to sort: the zero the device gives when every row is ignored
+        loss = x2d.sum() * 0.0
+        loss.loss64 = torch.zeros((), dtype=torch.float64, device=x2d.device)
+        loss.status = torch.zeros(1, dtype=torch.int32, device=x2d.device)
+        return loss
+    x = _f32c(x2d)
+    y = labels.reshape(-1).to(device=x.device, dtype=torch.int64).contiguous()
+    aux = {}
+    loss = _Lovasz.apply(x, y, from_logits, [int(o) for o in offsets], ignore, mode, mask, aux)
+    loss.status = aux["status"]
+    loss.loss64 = aux["state"][0]
+    if VALIDATE_LABELS and int(loss.status.item()) != 0:   # a host sync: debugging / validation runs only
+        raise IndexError(f"{name}: a label is outside [0, {C}) and is not the ignore value {ignore}")
+    return loss
+
+
+def lovasz_softmax(probas, labels, classes='present', per_image=False, ignore=None) -> torch.Tensor:
+    """Multi-class Lovasz-softmax loss, same call as ``mopa/common/utils/loss.py:122``: ``probas`` (P, C) or (B, C, H, W) class
+    probabilities, ``labels`` (P,) or (B, H, W); ``classes``: 'present' (classes with a labelled row), 'all', or a list;
+    ``per_image``: the mean of the per-image losses (the first dimension of a 4-D input; at most 32 images); ``ignore``: void label.
+
+    One forward call of a fixed number of launches (a segmented radix sort per class, integer running counts, float64 Jaccard
+    weights) and one backward launch; nothing is read back.  The result carries ``.loss64`` (0-d float64 tensor, the value before its
+    one rounding to float32) and ``.status`` (int32 tensor: bit 0 a label outside [0, C) that is not ``ignore``).
+
+    Deviations from the reference (DESIGN.md section 4): equal errors keep ascending row order (``torch.sort`` leaves ties open);
+    no valid row, or no selected class, gives 0 with a zero gradient (the reference returns a (0, C) tensor when every row is
+    ignored and raises IndexError at exactly one valid row); a label outside [0, C) is foreground for no class and is recorded, not
+    raised (``VALIDATE_LABELS`` checks after the call, as in ``seg_ce``); ``C == 1``, the sigmoid branch, raises ValueError."""
+    if probas.dim() == 3:
+        raise ValueError("lovasz_softmax: a (B, H, W) input is the reference's sigmoid branch (C == 1), which is not supported")
+    if probas.dim() == 4:
+        B, C, H, W = probas.shape
+        x = probas.permute(0, 2, 3, 1).reshape(-1, C)   # one strided copy on the device; autograd routes the gradient back
+        offsets = [b * H * W for b in range(B + 1)] if per_image else [0, B * H * W]
+    elif probas.dim() == 2:
+        if per_image:
+            raise ValueError("lovasz_softmax: per_image=True needs a (B, C, H, W) input; for row segments of a (P, C) input use "
+                             "lovasz_softmax_logits(..., segments=) or one call per segment")
+        x, offsets = probas, [0, probas.shape[0]]
+    else:
+        raise ValueError(f"lovasz_softmax: probas must be (P, C) or (B, C, H, W), not {tuple(probas.shape)}")
+    return _lovasz_call("lovasz_softmax", x, labels, False, offsets, ignore, classes)
+
+
+class Lovasz_softmax(torch.nn.Module):
+    """``mopa/common/utils/loss.py:191-199``: the module form of ``lovasz_softmax``."""
+
+    def __init__(self, classes='present', per_image=False, ignore=None):
+        super().__init__()
+        self.classes, self.per_image, self.ignore = classes, per_image, ignore
+
+    def forward(self, probas, labels):
+        return lovasz_softmax(probas, labels, self.classes, self.per_image, self.ignore)
+
+
+def lovasz_softmax_logits(logits, labels, classes='present', ignore_index: int = -100, segments=None) -> torch.Tensor:
+    """``lovasz_softmax(softmax_lastdim(logits), labels, classes, ignore=ignore_index)`` for (P, C) logits without the (P, C)
+    probability plane in memory: the kernels form p on the fly with the device function of ``softmax_lastdim`` (the same bits, so
+    ``.loss64`` equals the two-step form's exactly) and the backward returns d loss / d logits, accumulated in float64 from float64
+    coefficients and rounded once.  ``segments``: S + 1 row offsets (at most 32 segments, e.g. the scans of a merged batch): every
+    segment is its own loss and the result is their mean, as ``per_image=True`` does for images."""
+    if logits.dim() != 2:
+        raise ValueError(f"lovasz_softmax_logits: logits must be (P, C), not {tuple(logits.shape)}")
+    offsets = [0, logits.shape[0]] if segments is None else [int(o) for o in segments]
+    return _lovasz_call("lovasz_softmax_logits", logits, labels, True, offsets, ignore_index, classes)

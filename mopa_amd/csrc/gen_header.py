@@ -66,6 +66,17 @@ SECTIONS = [
  * guard.  No floating-point atomics: the same bits on every run.  `status` (int32 on the device, never read back by the call): bit 0 the
  * guard fired, bit 1 Jacobi hit its sweep bound, bit 2 an eigenvalue was <= 0.  The arithmetic is stated in DESIGN.md section 4;
  * yardstick tests/_coral_reference.py, held against the reference's float64 autograd."""),
+    ("lovasz.hip", """Lovasz-softmax loss on the device: lovasz_softmax / Lovasz_softmax of mopa/common/utils/loss.py:107-199, for float32
+ * probabilities (P, C) with 2 <= C <= 64, or from logits (the probabilities are formed on the fly with mopa_softmax_fwd's bits and
+ * never stored).  Per (row segment, class): key e = |fg - p| (one float32 operation), a stable LSD radix sort of (key bits, row)
+ * pairs -- descending e, equal keys in ascending row order, ignored rows last -- with per-block digit histograms in LDS and scatter
+ * offsets from a scan of the block x digit table, integer running counts of the foreground along the order, float64 Jaccard weights
+ * w_k = J_k - J_{k-1}, L_c = sum e_k w_k in float64 in a fixed order; the loss is the mean over the selected classes and then over
+ * the segments ('present' / 'all' / a list; up to 32 segments for per_image=True).  sign(p - fg) w goes into a coefficient plane,
+ * all the backward reads.  Class and segment are grid dimensions: the same launches for every P, C and label content; a class that
+ * is not selected costs no sort work; no host read, no floating-point atomics: the same bits on every run.  `status` (int32 on the
+ * device): bit 0 a label outside [0, C) that is not the ignore value (foreground for no class).  The arithmetic is stated in
+ * DESIGN.md section 4; yardstick tests/_lovasz_reference.py, held against the reference's own float32 result."""),
     ("pseudo.hip", """Pseudo-label update of the MoPA phase on the device (SURVEY 8f-3): EMA teacher (torch_ema update rule,
  * mopa/train/train_xmuda_mopa.py:221-226,587-591), entropy-weighted 2D/3D fusion (:282-291 with mopa/models/losses.py:10-19)
  * and the per-class median refinement (mopa/data/utils/refine_pseudo_labels.py:5-22), without host round trips."""),

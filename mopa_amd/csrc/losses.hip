@@ -7,6 +7,7 @@
 // Reference call sites (all in mopa/train/train_xmuda_mopa.py): KL :389-398,:440-445; CE :354-363,:456-465,:563-567;
 // softmax + mask_cons_loss :472-480 with mopa/common/utils/loss.py:241-283.  Oracle: oracle/losses.py.
 #include "common.h"
+#include "softmax_row.h"   // row_lse, row_softmax_at: shared with lovasz.hip
 
 #define MAXC 64
 #define LOSS_BLOCK 256
@@ -20,14 +21,6 @@ __device__ __forceinline__ double block_sum_d(double v, double* lds) {
   double t = 0.0;
   for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += lds[k];
   return t;
-}
-
-__device__ __forceinline__ float row_lse(const float* __restrict__ z, int C) {
-  float mx = z[0];
-  for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += expf(z[c] - mx);
-  return mx + logf(s);
 }
 
 // ------------------------------------------------------------------------------------------ softmax KL
@@ -742,7 +735,7 @@ __global__ void k_softmax_fwd(const float* __restrict__ z, int64_t N, int C, flo
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
     const float* zr = z + i * C;
     const float l = row_lse(zr, C);
-    for (int c = 0; c < C; ++c) p[i * C + c] = expf(zr[c] - l);
+    for (int c = 0; c < C; ++c) p[i * C + c] = row_softmax_at(zr[c], l);
   }
 }
 // dz = p * (dp - sum_c dp*p)
