@@ -19,8 +19,10 @@
 #include "common.h"
 #include "wino4.h"
 #include "weight_forms.h"
+#include "slabsum.h"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 struct ConvGeom {
   int B, IH, IW, OHl, OWl, OHa, OWa;
@@ -912,16 +914,10 @@ static bool stem_wgrad_mfma(const ConvGeom& g) {
 template <int EW>
 __global__ __launch_bounds__(256) void k_reduce_slabs2(const float* __restrict__ slabs, int nsplit, int64_t n, float* __restrict__ dw,
                                                         int accumulate, int oihw, int taps, int Cin, int Cout) {
-  constexpr int NL = 256 / EW;
-  __shared__ float red[NL][EW + 1];
+  __shared__ float red[256 / EW][EW + 1];
   const int el = threadIdx.x % EW, cl = threadIdx.x / EW;
   const int64_t i = (int64_t)blockIdx.x * EW + el;
-  float s = 0.f;
-  if (i < n)
-#pragma unroll 8
-    for (int c = cl; c < nsplit; c += NL) s += slabs[(int64_t)c * n + i];
-  red[cl][el] = s;
-  __syncthreads();
+  slab_lane_sums<EW>(red, slabs, nsplit, n, i, i < n);
   if (cl == 0 && i < n) {
     int64_t o = i;
     if (oihw) {   // i = (tap * Cin + ci) * Cout + co  ->  torch's parameter layout [co][ci][tap]
@@ -930,20 +926,23 @@ __global__ __launch_bounds__(256) void k_reduce_slabs2(const float* __restrict__
       const int ci = (int)(r % Cin), tap = (int)(r / Cin);
       o = ((int64_t)co * Cin + ci) * taps + tap;
     }
-    float t = accumulate ? dw[o] : 0.f;
-#pragma unroll
-    for (int k = 0; k < NL; ++k) t += red[k][el];
-    dw[o] = t;
+    dw[o] = slab_combine<EW>(red, el, accumulate ? dw[o] : 0.f);
   }
 }
-static inline int reduce_ew(int64_t n) { return n >= 64 * 512 ? 64 : n >= 32 * 512 ? 32 : 16; }
+// The element width of a reduction over n-element slabs, and its one dispatch: launch(std::integral_constant<int, EW>).
+constexpr int reduce_ew(int64_t n) { return n >= 64 * 512 ? 64 : n >= 32 * 512 ? 32 : 16; }
+template <typename Launch>
+static void with_reduce_ew(int64_t n, Launch&& launch) {
+  const int ew = reduce_ew(n);
+  if (ew == 64) launch(std::integral_constant<int, 64>());
+  else if (ew == 32) launch(std::integral_constant<int, 32>());
+  else launch(std::integral_constant<int, 16>());
+}
 static void reduce_slabs2_launch(const float* slabs, int ns, int64_t n, float* dw, int accumulate, int oihw, int taps, int Cin, int Cout,
                                  hipStream_t st) {
-  const int ew = reduce_ew(n);
-  const unsigned nb = (unsigned)cdiv64(n, ew);
-  if (ew == 64) k_reduce_slabs2<64><<<nb, 256, 0, st>>>(slabs, ns, n, dw, accumulate, oihw, taps, Cin, Cout);
-  else if (ew == 32) k_reduce_slabs2<32><<<nb, 256, 0, st>>>(slabs, ns, n, dw, accumulate, oihw, taps, Cin, Cout);
-  else k_reduce_slabs2<16><<<nb, 256, 0, st>>>(slabs, ns, n, dw, accumulate, oihw, taps, Cin, Cout);
+  with_reduce_ew(n, [&](auto ew) {
+    k_reduce_slabs2<ew()><<<(unsigned)cdiv64(n, ew()), 256, 0, st>>>(slabs, ns, n, dw, accumulate, oihw, taps, Cin, Cout);
+  });
 }
 
 static int wgrad_ntap(const ConvGeom& g) {
@@ -1134,24 +1133,16 @@ __global__ __launch_bounds__(256, 3) void k_convt_wgrad_mfma(const float* __rest
 template <int EW>
 __global__ __launch_bounds__(256) void k_reduce_slabs_convt(const float* __restrict__ slabs, int nsplit, int64_t n, float* __restrict__ dw,
                                                              int accumulate, int Cin, int Cout) {
-  constexpr int NL = 256 / EW;
-  __shared__ float red[NL][EW + 1];
+  __shared__ float red[256 / EW][EW + 1];
   const int el = threadIdx.x % EW, cl = threadIdx.x / EW;
   const int64_t i = (int64_t)blockIdx.x * EW + el;
-  float s = 0.f;
-  if (i < n)
-#pragma unroll 8
-    for (int c = cl; c < nsplit; c += NL) s += slabs[(int64_t)c * n + i];
-  red[cl][el] = s;
-  __syncthreads();
+  slab_lane_sums<EW>(red, slabs, nsplit, n, i, i < n);
   if (cl == 0 && i < n) {   // i = (tap * Cin + ci) * Cout + co
     const int co = (int)(i % Cout);
     const int64_t r = i / Cout;
     const int ci = (int)(r % Cin), tap = (int)(r / Cin);
     const int64_t o = ((int64_t)ci * Cout + co) * 4 + tap;
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < NL; ++k) t += red[k][el];
+    const float t = slab_combine<EW>(red, el, 0.f);
     dw[o] = (accumulate ? dw[o] : 0.f) + t;
   }
 }
@@ -1187,11 +1178,9 @@ MOPA_API int mopa_convt_bwd_weight(const float* in, const float* dy, float* dwei
   dim3 grid(1, (g.Cin / 64) * (g.Cout / 64), ns);
   k_convt_wgrad_mfma<<<grid, 256, 0, st>>>(in, dy, slabs, g, mps);
   const int64_t n1 = (int64_t)g.Cin * g.Cout, n = 4 * n1;
-  const int ew = reduce_ew(n1);
-  const unsigned nb = (unsigned)cdiv64(n, ew);
-  if (ew == 64) k_reduce_slabs_convt<64><<<nb, 256, 0, st>>>(slabs, ns, n, dweight, flags & 1, g.Cin, g.Cout);
-  else if (ew == 32) k_reduce_slabs_convt<32><<<nb, 256, 0, st>>>(slabs, ns, n, dweight, flags & 1, g.Cin, g.Cout);
-  else k_reduce_slabs_convt<16><<<nb, 256, 0, st>>>(slabs, ns, n, dweight, flags & 1, g.Cin, g.Cout);
+  with_reduce_ew(n1, [&](auto ew) {
+    k_reduce_slabs_convt<ew()><<<(unsigned)cdiv64(n, ew()), 256, 0, st>>>(slabs, ns, n, dweight, flags & 1, g.Cin, g.Cout);
+  });
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
 }
@@ -1426,22 +1415,17 @@ static bool stem_strip_geom(const ConvGeom& g) {
          g.OOY == 0 && g.OOX == 0 && g.OHa == g.OHl && g.OWa == g.OWl && g.IH >= g.OHl + 6 && g.IW >= g.OWl + 7 && g.B > 0 && g.OHl > 0 &&
          g.OWl > 0 && (int64_t)g.B * g.IH * g.IW < (1ll << 29);
 }
-// k_reduce_slabs2<16>'s sums of the stem's slabs (14,336 elements: reduce_ew's narrowest form) written through k_stem_relayout's
+// k_reduce_slabs2's sums of the stem's slabs (14,336 elements: reduce_ew's narrowest form) written through k_stem_relayout's
 // inverse map into torch's [64][3][7][7] gradient: reduction and relayout of the stem's weight gradient as one launch, same bits.
 __global__ __launch_bounds__(256) void k_reduce_slabs_stem(const float* __restrict__ slabs, int nsplit, float* __restrict__ dw, int accumulate) {
-  constexpr int EW = 16, NL = 256 / EW, n = STEM_ROWS * 64;
-  __shared__ float red[NL][EW + 1];
+  constexpr int n = STEM_ROWS * 64, EW = reduce_ew(n);
+  static_assert(n % EW == 0, "whole blocks: no bounds test");
+  __shared__ float red[256 / EW][EW + 1];
   const int el = threadIdx.x % EW, cl = threadIdx.x / EW;
   const int i = blockIdx.x * EW + el;
-  float s = 0.f;
-#pragma unroll 8
-  for (int c = cl; c < nsplit; c += NL) s += slabs[(int64_t)c * n + i];
-  red[cl][el] = s;
-  __syncthreads();
+  slab_lane_sums<EW>(red, slabs, nsplit, n, i, true);   // (the grid is n / EW blocks: every thread is live)
   if (cl == 0) {
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < NL; ++k) t += red[k][el];
+    const float t = slab_combine<EW>(red, el, 0.f);
     const int o = i % 64;
     int r = i / 64;
     const int k16 = r % 16; r /= 16;
@@ -1460,7 +1444,6 @@ static int stem_wgrad2_launch(const float* in, const float* dy, float* dweight, 
   const int accumulate = flags & 1, param = (flags >> 1) & 1;
   if (!stem_strip_geom(g) || !in || !dy || !dweight || (flags & ~3)) return MOPA_ERR_ARG;
   if (!bn && (g.ld_out < 64 || (g.ld_out & 3))) return MOPA_ERR_ARG;
-  static_assert(STEM_ROWS * 64 < 32 * 512, "k_reduce_slabs_stem is k_reduce_slabs2<16>");
   if (ws_bytes < mopa_conv2d_wgrad_workspace_bytes(geom_host)) return MOPA_ERR_WORKSPACE;
   int ns, mps;
   wgrad_split(g, &ns, &mps);
@@ -1472,7 +1455,7 @@ static int stem_wgrad2_launch(const float* in, const float* dy, float* dweight, 
   else if (param) k_stem_wgrad_strip<false, true><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, StemBn{});
   else k_stem_wgrad_strip<false, false><<<ns, 256, 0, st>>>(in, dy, slabs, g, mps, StemBn{});
   const int n = STEM_ROWS * 64;
-  if (param) k_reduce_slabs_stem<<<n / 16, 256, 0, st>>>(slabs, ns, dweight, accumulate);
+  if (param) k_reduce_slabs_stem<<<n / reduce_ew(n), 256, 0, st>>>(slabs, ns, dweight, accumulate);
   else reduce_slabs2_launch(slabs, ns, n, dweight, accumulate, 0, 14, 16, 64, st);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
@@ -1664,11 +1647,7 @@ __global__ __launch_bounds__(256) void k_wino_dw(const float* __restrict__ slabs
   __shared__ float red[16][17];
   const int e = threadIdx.x & 15, p = threadIdx.x >> 4;
   const int64_t i = (int64_t)blockIdx.x * 16 + e;
-  float s = 0.f;
-  if (i < n)
-#pragma unroll 8
-    for (int c = 0; c < nsplit; ++c) s += slabs[((int64_t)c * 16 + p) * n + i];
-  red[p][e] = s;
+  red[p][e] = slab_point_sum<16>(slabs, nsplit, n, i, p, i < n);
   __syncthreads();
   if (p != 0 || i >= n) return;
   float u[4][4];
@@ -1681,15 +1660,12 @@ __global__ __launch_bounds__(256) void k_wino_dw(const float* __restrict__ slabs
     t[1][j] = 0.5f * (u[1][j] - u[2][j]);
     t[2][j] = 0.5f * (u[1][j] + u[2][j]) + u[3][j];
   }
-  // igemm layout [tap][ci][co] (i = ci * Cout + co), or torch's OIHW [co][ci][tap]
-  const int co = (int)(i % Cout), ci = (int)(i / Cout);
-  const int64_t base = oihw ? ((int64_t)co * Cin + ci) * 9 : i, step = oihw ? 1 : n;
+  int64_t base, step;
+  slab_dw_3x3(i, n, oihw, Cin, Cout, base, step);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {  // (.) G
-    float g0 = t[a][0] + 0.5f * (t[a][1] + t[a][2]), g1 = 0.5f * (t[a][1] - t[a][2]), g2 = 0.5f * (t[a][1] + t[a][2]) + t[a][3];
-    float* d = dw + base + (int64_t)(a * 3) * step;
-    if (accumulate) { g0 += d[0]; g1 += d[step]; g2 += d[2 * step]; }
-    d[0] = g0; d[step] = g1; d[2 * step] = g2;
+    const float g0 = t[a][0] + 0.5f * (t[a][1] + t[a][2]), g1 = 0.5f * (t[a][1] - t[a][2]), g2 = 0.5f * (t[a][1] + t[a][2]) + t[a][3];
+    slab_store_row(dw + base + (int64_t)(a * 3) * step, step, accumulate, g0, g1, g2);
   }
 }
 
@@ -1706,14 +1682,7 @@ __global__ __launch_bounds__(256) void k_wino4_dw(const float* __restrict__ slab
 #pragma unroll
   for (int k = 0; k < (36 + NQ - 1) / NQ; ++k) {
     const int p = q + k * NQ;
-    if (p < 36) {
-      float s = 0.f;
-      if (i < n) {
-#pragma unroll 8
-        for (int c = 0; c < nsplit; ++c) s += slabs[((int64_t)c * 36 + p) * n + i];
-      }
-      red[p][e] = s;
-    }
+    if (p < 36) red[p][e] = slab_point_sum<36>(slabs, nsplit, n, i, p, i < n);
   }
   __syncthreads();
   if (q != 0 || i >= n) return;
@@ -1726,27 +1695,23 @@ __global__ __launch_bounds__(256) void k_wino4_dw(const float* __restrict__ slab
     t[1][j] = (1.f / 6.f) * (u2 - u1) + (1.f / 12.f) * (u3 - u4);
     t[2][j] = -(1.f / 6.f) * (u1 + u2) + (1.f / 6.f) * (u3 + u4) + u5;
   }
-  const int co = (int)(i % Cout), ci = (int)(i / Cout);
-  const int64_t base = oihw ? ((int64_t)co * Cin + ci) * 9 : i, step = oihw ? 1 : n;
+  int64_t base, step;
+  slab_dw_3x3(i, n, oihw, Cin, Cout, base, step);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {   // (.) G
-    float g0 = 0.25f * t[a][0] - (1.f / 6.f) * (t[a][1] + t[a][2]) + (1.f / 24.f) * (t[a][3] + t[a][4]);
-    float g1 = (1.f / 6.f) * (t[a][2] - t[a][1]) + (1.f / 12.f) * (t[a][3] - t[a][4]);
-    float g2 = -(1.f / 6.f) * (t[a][1] + t[a][2]) + (1.f / 6.f) * (t[a][3] + t[a][4]) + t[a][5];
-    float* d = dw + base + (int64_t)(a * 3) * step;
-    if (accumulate) { g0 += d[0]; g1 += d[step]; g2 += d[2 * step]; }
-    d[0] = g0; d[step] = g1; d[2 * step] = g2;
+    const float g0 = 0.25f * t[a][0] - (1.f / 6.f) * (t[a][1] + t[a][2]) + (1.f / 24.f) * (t[a][3] + t[a][4]);
+    const float g1 = (1.f / 6.f) * (t[a][2] - t[a][1]) + (1.f / 12.f) * (t[a][3] - t[a][4]);
+    const float g2 = -(1.f / 6.f) * (t[a][1] + t[a][2]) + (1.f / 6.f) * (t[a][3] + t[a][4]) + t[a][5];
+    slab_store_row(dw + base + (int64_t)(a * 3) * step, step, accumulate, g0, g1, g2);
   }
 }
 
 // (for wino4wg.hip: the slab sum + G^T dU G epilogue of an F(4x4) weight gradient whose slabs another kernel produced)
 int wino4_dw_launch(const float* slabs, int nsplit, int Cin, int Cout, float* dweight, int flags, hipStream_t st) {
   const int64_t n = (int64_t)Cin * Cout;
-  const int ew = reduce_ew(n), acc = flags & 1, oihw = (flags >> 1) & 1;
-  const unsigned nb = (unsigned)cdiv64(n, ew);
-  if (ew == 64) k_wino4_dw<64><<<nb, 256, 0, st>>>(slabs, nsplit, n, dweight, acc, oihw, Cin, Cout);
-  else if (ew == 32) k_wino4_dw<32><<<nb, 256, 0, st>>>(slabs, nsplit, n, dweight, acc, oihw, Cin, Cout);
-  else k_wino4_dw<16><<<nb, 256, 0, st>>>(slabs, nsplit, n, dweight, acc, oihw, Cin, Cout);
+  with_reduce_ew(n, [&](auto ew) {
+    k_wino4_dw<ew()><<<(unsigned)cdiv64(n, ew()), 256, 0, st>>>(slabs, nsplit, n, dweight, flags & 1, (flags >> 1) & 1, Cin, Cout);
+  });
   return hipGetLastError() == hipSuccess ? MOPA_OK : MOPA_ERR_LAUNCH;
 }
 

@@ -15,6 +15,7 @@
 // JoinTable buffer); weights [K][Cin][Cout] fp32.
 #include "common.h"
 #include "sprun_pack.h"
+#include "slabsum.h"
 #ifdef MOPA_EXP_RING   // round-4 experiment (profiles/experiments/spconv_ring.hip, build_ring.sh): not in the shipped library
 #include "spconv_ring.h"
 #endif
@@ -1542,25 +1543,15 @@ __global__ __launch_bounds__(64 * WG2_NWV) void k_spconv_wgrad2(const int* __res
     }
 }
 
-// dw[i] (+)= sum_c slabs[c][i].  16 chunk-lanes per element sum strided chunks, then a fixed-order LDS reduction:
-// deterministic, and short even with ~1000 chunks.
+// dw[i] (+)= sum_c slabs[c][i].  16 chunk-lanes per element sum strided chunks, then a fixed-order LDS reduction (slabsum.h,
+// "dw first"): deterministic, and short even with ~1000 chunks.
 __global__ __launch_bounds__(256) void k_reduce_slabs(const float* __restrict__ slabs, int nchunks, int64_t n, float* __restrict__ dw,
                                                        int accumulate) {
   __shared__ float red[16][17];
   const int el = threadIdx.x & 15, cl = threadIdx.x >> 4;
   const int64_t i = (int64_t)blockIdx.x * 16 + el;
-  float s = 0.f;
-  if (i < n)
-#pragma unroll 8
-    for (int c = cl; c < nchunks; c += 16) s += slabs[(int64_t)c * n + i];
-  red[cl][el] = s;
-  __syncthreads();
-  if (cl == 0 && i < n) {
-    float t = accumulate ? dw[i] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) t += red[k][el];
-    dw[i] = t;
-  }
+  slab_lane_sums<16>(red, slabs, nchunks, n, i, i < n);
+  if (cl == 0 && i < n) dw[i] = slab_combine<16>(red, el, accumulate ? dw[i] : 0.f);
 }
 
 // The stem's weight gradient (one input channel): dW[o][c] = sum_i in[nbr[o][i]] * dout[i][c] -- a reduction over the rows, no GEMM.

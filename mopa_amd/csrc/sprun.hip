@@ -703,7 +703,7 @@ __global__ __launch_bounds__(512) void k_wgrad_run(const int* __restrict__ hdr, 
 }
 
 // dW[o][e] (+)= the slabs of offset o's pieces, in piece order: block = 64 elements (16 float4 lanes: 256-byte runs) x 16 piece-lanes
-// that sum strided pieces, then a fixed-order combine (as k_reduce_slabs: deterministic)
+// that sum strided pieces, then a fixed-order combine: slabsum.h's order (EW = 16, "dw first") in this kernel's own text
 __global__ __launch_bounds__(256) void k_wgrad_run_reduce(const int* __restrict__ hdr, int K, int S, const float* __restrict__ slabs, int n_e,
                                                           float* __restrict__ dw, int accumulate) {
   __shared__ f32x4r red[16][17];
