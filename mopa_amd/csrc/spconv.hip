@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64) void k_spconv_fwd(const int* __restrict__ nbr, 
 // Column-group width (in 16-column tiles) and row-tile height.  NTW must divide NT (vector B loads); columns are
 // split further whenever a launch would otherwise hold fewer than ~2k waves.  128-row tiles only where a 64-row tile
 // sees < 16 rules per offset on average (the sparse shallow levels), so MFMA row groups are better filled.
-static void fwd_plan(int K, int A_out, int cout, int* ntw, int* tmr) {
+static void fwd_plan(int K, int64_t A_out, int cout, int* ntw, int* tmr) {
   const int NT = (cout + 15) / 16;
   // measured (profiles/r1_*): tiles >= ~1500 already fill the chip with one wave per tile and all columns (the row
   // gathers are not repeated); below that the per-wave serial chain over the offsets dominates and the columns are
@@ -193,22 +193,6 @@ static int launch_fwd(const int* nbr, int K, int A_out, const float* in, int ld_
   else
     k_spconv_fwd<NTW, NA, false><<<grid, 64, 0, st>>>(nbr, K, A_out, in, ld_in, cin, W, cout, w_flip, out, ld_out);
   return hipGetLastError() == hipSuccess ? MOPA_OK : MOPA_ERR_LAUNCH;
-}
-
-template <int NTW>
-static int dispatch_fwd(const int* nbr, int K, int A_out, const float* in, int ld_in, int cin, const float* W, int cout,
-                        int w_flip, float* out, int ld_out, bool aligned, hipStream_t st) {
-#define FW(C) return launch_fwd<NTW, C>(nbr, K, A_out, in, ld_in, cin, W, cout, w_flip, out, ld_out, aligned, st)
-  switch ((cin + 15) / 16) {
-    case 1: FW(1);
-    case 2: FW(2);
-    case 3: FW(3);
-    case 4: FW(4);
-    default: break;
-  }
-  if (cin <= 128) FW(8);
-  FW(12);
-#undef FW
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -263,31 +247,39 @@ static int launch_stem(const int* nbr, int K, int A_out, const float* in, int ld
   return hipGetLastError() == hipSuccess ? MOPA_OK : MOPA_ERR_LAUNCH;
 }
 
-// out[A_out][cout] (row stride ld_out) = sum_o in[nbr[o][.]] @ W[w_flip ? K-1-o : o]
+// Which kernel mopa_spconv_fwd runs on a table of `rows` rows (SPK value, sprun_pack.h).  aligned: 16-channel multiples, row strides
+// of whole float4 and 16-byte pointers; stem_ok: the output rows can take float4 stores.
+static int pick_fwd(int K, int64_t rows, int cin, int cout, bool aligned, bool stem_ok) {
+  static const int stem_on = getenv("MOPA_SPCONV_STEM") ? atoi(getenv("MOPA_SPCONV_STEM")) : 1;   // A/B switch
+  if (stem_on && cin <= 4 && (cout == 16 || cout == 32) && stem_ok) return SPK(SPK_STEM, cin, cout / 16, 0, 0);   // scalar gathers
+  int ntw, tmr;
+  fwd_plan(K, rows, cout, &ntw, &tmr);
+  if (!aligned) ntw = 1;
+  const int c16 = (cin + 15) / 16;
+  const int na = c16 <= 4 ? c16 : cin <= 128 ? 8 : 12;
+  return SPK(SPK_FWD, ntw, na, 0, 0) | (aligned ? SPK_FLAG : 0);
+}
+
+// out[A_out][cout] (row stride ld_out) = sum_o in[nbr[o][.]] @ W[w_flip & 1 ? K-1-o : o]; w_flip bits 8-30: see sprun_pack.h
 MOPA_API int mopa_spconv_fwd(const int32_t* nbr, int32_t K, int32_t num_out, const float* in, int32_t ld_in,
                              int32_t cin, const float* weight, int32_t cout, int32_t w_flip, float* out,
                              int32_t ld_out, void* stream) {
   if (K <= 0 || K > 27 || num_out <= 0 || cin <= 0 || cin > 192 || cout <= 0 || ld_in < cin || ld_out < cout) return MOPA_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
-  static const int stem_on = getenv("MOPA_SPCONV_STEM") ? atoi(getenv("MOPA_SPCONV_STEM")) : 1;   // A/B switch
-  if (stem_on && cin <= 4 && (cout == 16 || cout == 32) && ld_out % 4 == 0 && ((uintptr_t)out & 15) == 0) {   // the stem: scalar gathers
-    switch (cin) {
-      case 1: return launch_stem<1>(nbr, K, num_out, in, ld_in, weight, cout, w_flip, out, ld_out, st);
-      case 2: return launch_stem<2>(nbr, K, num_out, in, ld_in, weight, cout, w_flip, out, ld_out, st);
-      case 3: return launch_stem<3>(nbr, K, num_out, in, ld_in, weight, cout, w_flip, out, ld_out, st);
-      default: return launch_stem<4>(nbr, K, num_out, in, ld_in, weight, cout, w_flip, out, ld_out, st);
-    }
-  }
   const bool aligned = (cin % 16 == 0) && (cout % 16 == 0) && (ld_in % 4 == 0) && (ld_out % 4 == 0) &&
                        (((uintptr_t)in | (uintptr_t)out | (uintptr_t)weight) % 16 == 0);
-  int ntw, tmr;
-  fwd_plan(K, num_out, cout, &ntw, &tmr);
-  if (!aligned) ntw = 1;
-  switch (ntw) {
-    case 1: return dispatch_fwd<1>(nbr, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, aligned, st);
-    case 2: return dispatch_fwd<2>(nbr, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, aligned, st);
-    case 3: return dispatch_fwd<3>(nbr, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, aligned, st);
-    default: return dispatch_fwd<4>(nbr, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, aligned, st);
+  const int pick = pick_fwd(K, spk_stated_rows(w_flip, num_out), cin, cout, aligned, ld_out % 4 == 0 && ((uintptr_t)out & 15) == 0);
+  w_flip &= 1;
+  switch (SPK_KERNEL(pick)) {
+#define ST(C) case SPK(SPK_STEM, C, 1, 0, 0): case SPK(SPK_STEM, C, 2, 0, 0): return launch_stem<C>(nbr, K, num_out, in, ld_in, weight, cout, w_flip, out, ld_out, st);
+    ST(1) ST(2) ST(3) ST(4)
+#undef ST
+#define FW(N, C) case SPK(SPK_FWD, N, C, 0, 0): return launch_fwd<N, C>(nbr, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, aligned, st);
+#define FWN(N) FW(N, 1) FW(N, 2) FW(N, 3) FW(N, 4) FW(N, 8) FW(N, 12)
+    FWN(1) FWN(2) FWN(3) FWN(4)
+#undef FWN
+#undef FW
+    default: return MOPA_ERR_ARG;
   }
 }
 
@@ -1085,10 +1077,9 @@ __global__ __launch_bounds__(64 * NWV) void k_spconv_t4(const int* __restrict__ 
 
 template <int NTW, int NKU, int D, int NWV = 4>
 static int launch_t4(const int* gs, const int* go, const int* gi, const int* gout, int K, int A_out, const float* in, int ld_in,
-                     int cin, const float* Wp, int cout, int w_flip, float* out, int ld_out, hipStream_t st) {
+                     int cin, const float* Wp, int cout, int w_flip, float* out, int ld_out, bool part, hipStream_t st) {
   constexpr int CP = NTW * 16, LD = CP + T4_PAD, MS = (NWV == 1 ? 40 : 48) + 4;
   const size_t lds = NWV * 65 * LD * 4 + MS * 100;
-  const bool part = ((cin >> 4) % NKU) != 0;
   dim3 grid((unsigned)cdiv64(A_out, 64), cout / CP);
 #define T4_GO(P)                                                                                                          \
   {                                                                                                                       \
@@ -1144,7 +1135,7 @@ static inline size_t blk_lds_bytes(int ntw, int cin) {
 
 // Columns per block: the widest of 64/32/16 that divides Cout's 16-column tiles, fits 64 KB of LDS and still leaves
 // >= 512 blocks (2 per CU) when the layer allows it.
-static int blk_plan(int A_out, int cin, int cout) {
+static int blk_plan(int64_t A_out, int cin, int cout) {
   const int NT = (cout + 15) / 16;
   const int64_t tiles4 = cdiv64(cdiv64(A_out, 64), SPB_WAVES);
   int best = 1;
@@ -1160,12 +1151,12 @@ static int blk_plan(int A_out, int cin, int cout) {
 }
 
 // Offsets are split over grid.z when the launch would otherwise hold < ~1000 blocks (and a workspace is given).
-static int blk_osplit(int K, int A_out, int cout, int ntw) {
+static int blk_osplit(int K, int64_t A_out, int cout, int ntw) {
   const int NT = (cout + 15) / 16;
   const int64_t blocks = cdiv64(cdiv64(A_out, 64), SPB_WAVES) * ((NT + ntw - 1) / ntw);
   int64_t s = cdiv64(3072, blocks);
   if (s > 9) s = 9;
-  const int64_t cap_bytes = (48ll << 20) / ((int64_t)A_out * cout * 4 + 1);  // partial copies stay below ~48 MB
+  const int64_t cap_bytes = (48ll << 20) / (A_out * cout * 4 + 1);  // partial copies stay below ~48 MB
   if (s > cap_bytes) s = cap_bytes;
   if (s > K / 2) s = K / 2;
   if (s < 1) s = 1;
@@ -1190,32 +1181,68 @@ static int launch_blk(const int* gs, const int* go, const int* gi, const int* go
   return hipGetLastError() == hipSuccess ? MOPA_OK : MOPA_ERR_LAUNCH;
 }
 
-template <int NTW>
-static int dispatch_blk_c(const int* gs, const int* go, const int* gi, const int* gout, int K, int A_out, const float* in,
-                          int ld_in, int cin, const float* W, int cout, int w_flip, float* out, int ld_out, bool aligned,
-                          float* part, int osplit, hipStream_t st) {
-#define RB(C) return launch_blk<NTW, C>(gs, go, gi, gout, K, A_out, in, ld_in, cin, W, cout, w_flip, out, ld_out, aligned, part, osplit, st)
-  const int c16 = (cin + 15) / 16;
-  if (c16 <= 4) {
-    switch (c16) {
-      case 1: RB(1);
-      case 2: RB(2);
-      case 3: RB(3);
-      default: RB(4);
-    }
-  }
-  if (c16 <= 8) RB(8);
-  if (c16 <= 12) RB(12);
-  return MOPA_ERR_ARG;
-#undef RB
-}
-
 MOPA_API size_t mopa_spconv_grouped_workspace_bytes(int32_t K, int32_t num_out, int32_t cout) {
   return align_up((size_t)9 * num_out * cout * sizeof(float), 256);  // upper bound: 9 partial copies of the output
 }
 
+// Which kernel mopa_spconv_fwd_grouped runs on a table of `rows` rows (SPK value, sprun_pack.h), or MOPA_ERR_ARG where the call is
+// refused.  has_ws: a workspace for `osplit` partial copies is at hand.
+//   packed weights: long levels one pipelined wave per tile (k_spconv_pipe), else k_spconv_t4 with four waves per (tile, column
+//   group) -- one wave on the long down/up tables; unpacked: 4-wave blocks with LDS-staged weights (k_spconv_blk).
+static int pick_grouped(int K, int64_t rows, int cin, int cout, bool packed, bool aligned, bool has_ws) {
+  if (packed) {
+    int pntw;
+    const int path = packed_plan(K, rows, cin, cout, &pntw);
+    if (!aligned || path == SP_BLK) return MOPA_ERR_ARG;
+    const int nkc = cin / 16;
+#ifdef MOPA_EXP_RING
+    if (path == SP_RING) return SPK(SPK_RING, pntw, 0, 0, 0);
+#endif
+#define T4P(N, KU, DD, WV) (SPK(SPK_T4, N, KU, DD, WV) | (nkc % (KU) ? SPK_FLAG : 0))   // PART: the last unit's chunks are clamped
+    if (path == SP_PIPE && cout == 16 && nkc == 2) return T4P(1, 2, 2, 1);   // 32 -> 16: one wave per tile with whole-Cin units (40 vs 42 us)
+    if (path == SP_PIPE) {
+      switch (cout / 16) {
+        case 1: return SPK(SPK_PIPE, 1, 0, 2, 0);    // MU 40: LDS 9.6 KB -> 16 waves / CU
+        case 2: return SPK(SPK_PIPE, 2, 0, 6, 0);    // MU 32: 13.0 KB -> 12
+        case 3: return SPK(SPK_PIPE, 3, 0, 6, 0);    // MU 40: 17.9 KB ->  8
+        default: return SPK(SPK_PIPE, 4, 0, 4, 0);   // MU 28: 20.9 KB ->  7
+      }
+    }
+    if (K != 27 && cdiv64(rows, 64) > 800) {   // long down/up tables: 17-28 us vs 20-34 on the dense-table kernel
+      if (pntw <= 2) return T4P(pntw, nkc < 4 ? nkc : 4, 2, 1);
+      return T4P(3, nkc < 3 ? nkc : 3, 2, 1);
+    }
+    // unit = group x NKU chunks: the whole Cin up to 64 channels, else 3-4 chunks per unit (registers: NKU*4*(1+NTW) per ring slot)
+    if (pntw == 1) {
+      if (nkc == 1) return T4P(1, 1, 4, 4);
+      if (nkc == 2) return T4P(1, 2, 2, 4);
+      if (nkc % 5 == 0) return T4P(1, 5, 2, 4);   // 80 / 160 channels: whole units, no padded chunk
+      if (nkc % 7 == 0) return T4P(1, 7, 2, 4);   // 112 / 224
+      if (nkc % 3 == 0) return T4P(1, 3, 2, 4);
+      return T4P(1, 4, 2, 4);
+    }
+    if (pntw == 2) {
+      if (nkc == 1) return T4P(2, 1, 2, 4);
+      if (nkc == 2) return T4P(2, 2, 2, 4);
+      if (nkc % 5 == 0) return T4P(2, 5, 2, 4);
+      if (nkc % 3 == 0) return T4P(2, 3, 2, 4);
+      return T4P(2, 4, 2, 4);
+    }
+    if (nkc == 1) return T4P(3, 1, 2, 4);
+    if (nkc == 2 || nkc == 4) return T4P(3, 2, 2, 4);
+    return T4P(3, 3, 2, 4);
+#undef T4P
+  }
+  const int ntw = aligned ? blk_plan(rows, cin, cout) : 1;
+  const int c16 = (cin + 15) / 16;
+  if (blk_lds_bytes(ntw, cin) > 64 * 1024 || c16 > 12) return MOPA_ERR_ARG;
+  const int osplit = (aligned && has_ws) ? blk_osplit(K, rows, cout, ntw) : 1;
+  return SPK(SPK_BLK, ntw, c16 <= 4 ? c16 : c16 <= 8 ? 8 : 12, 0, 0) | (aligned ? SPK_FLAG : 0) | osplit << 20;
+}
+
 // Same contract as mopa_spconv_fwd, on the grouped rulebook of the table (mopa_rulebook_groups_{count,fill}).
 // ws (optional, mopa_spconv_grouped_workspace_bytes) lets short levels split the filter offsets over more blocks.
+// w_flip bit 0 = mirrored filter offsets, bit 1 = weight is packed (mopa_spconv_pack_weight), bits 8-30: see sprun_pack.h.
 MOPA_API int mopa_spconv_fwd_grouped(const int32_t* grp_start, const int32_t* grp_o, const int32_t* grp_in,
                                      const int32_t* grp_out, int32_t K, int32_t num_out, const float* in, int32_t ld_in,
                                      int32_t cin, const float* weight, int32_t cout, int32_t w_flip, float* out,
@@ -1225,74 +1252,55 @@ MOPA_API int mopa_spconv_fwd_grouped(const int32_t* grp_start, const int32_t* gr
   const bool aligned = (cin % 16 == 0) && (cout % 16 == 0) && (ld_in % 4 == 0) && (ld_out % 4 == 0) &&
                        (((uintptr_t)in | (uintptr_t)out | (uintptr_t)weight) % 16 == 0);
   if (cin > ((w_flip & 2) ? 224 : 192)) return MOPA_ERR_ARG;
-  // long levels: one pipelined wave per tile (k_spconv_pipe, packed weights); short levels: 4-wave blocks with
-  // LDS-staged weights.  w_flip bit 0 = mirrored filter offsets, bit 1 = weight is packed (mopa_spconv_pack_weight).
   const int packed = (w_flip >> 1) & 1;
+  const int pick = pick_grouped(K, spk_stated_rows(w_flip, num_out), cin, cout, packed, aligned, ws != nullptr);
   w_flip &= 1;
-  if (packed) {
-    int pntw;
-    const int path = packed_plan(K, num_out, cin, cout, &pntw);
-    if (!aligned || path == SP_BLK) return MOPA_ERR_ARG;
-    // the pipelined kernels address input rows with 32-bit byte offsets (an input has at most 8x the output's rows)
-    if ((int64_t)num_out * 8 * ld_in * 4 >= (1ll << 32)) return MOPA_ERR_ARG;
-    const int nkc = cin / 16;
-#ifdef MOPA_EXP_RING
-    if (path == SP_RING)
-      return mopa_ring_launch(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, pntw, st);
-#endif
-    if (path == SP_PIPE && cout == 16 && nkc == 2)   // 32 -> 16: one wave per tile with whole-Cin units (40 vs 42 us)
-      return launch_t4<1, 2, 2, 1>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, st);
-    if (path == SP_PIPE) {
-#define PP(N, DD, MU) return launch_pipe<N, DD, MU>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, w_flip, out, ld_out, st)
-      switch (cout / 16) {
-        case 1: PP(1, 2, 40);   // LDS 9.6 KB -> 16 waves / CU
-        case 2: PP(2, 6, 32);   // 13.0 KB -> 12
-        case 3: PP(3, 6, 40);   // 17.9 KB ->  8
-        default: PP(4, 4, 28);  // 20.9 KB ->  7
-      }
-#undef PP
-    }
-    if (K != 27 && cdiv64(num_out, 64) > 800) {   // long down/up tables: 17-28 us vs 20-34 on the dense-table kernel
-#define T1(N, KU) return launch_t4<N, KU, 2, 1>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, st)
-      if (pntw == 1) { if (nkc == 1) T1(1, 1); if (nkc == 2) T1(1, 2); if (nkc == 3) T1(1, 3); T1(1, 4); }
-      if (pntw == 2) { if (nkc == 1) T1(2, 1); if (nkc == 2) T1(2, 2); if (nkc == 3) T1(2, 3); T1(2, 4); }
-      if (nkc == 1) T1(3, 1); if (nkc == 2) T1(3, 2); T1(3, 3);
-#undef T1
-    }
-#define T4(N, KU, DD) return launch_t4<N, KU, DD>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, st)
-    // unit = group x NKU chunks: the whole Cin up to 64 channels, else 3-4 chunks per unit (registers: NKU*4*(1+NTW) per ring slot)
-    if (pntw == 1) {
-      if (nkc == 1) T4(1, 1, 4);
-      if (nkc == 2) T4(1, 2, 2);
-      if (nkc % 5 == 0) T4(1, 5, 2);   // 80 / 160 channels: whole units, no padded chunk
-      if (nkc % 7 == 0) T4(1, 7, 2);   // 112 / 224
-      if (nkc % 3 == 0) T4(1, 3, 2);
-      T4(1, 4, 2);
-    }
-    if (pntw == 2) {
-      if (nkc == 1) T4(2, 1, 2);
-      if (nkc == 2) T4(2, 2, 2);
-      if (nkc % 5 == 0) T4(2, 5, 2);
-      if (nkc % 3 == 0) T4(2, 3, 2);
-      T4(2, 4, 2);
-    }
-    if (nkc == 1) T4(3, 1, 2);
-    if (nkc == 2 || nkc == 4) T4(3, 2, 2);
-    T4(3, 3, 2);
-#undef T4
-  }
-  const int ntw = aligned ? blk_plan(num_out, cin, cout) : 1;
-  if (blk_lds_bytes(ntw, cin) > 64 * 1024) return MOPA_ERR_ARG;
-  int osplit = (aligned && ws) ? blk_osplit(K, num_out, cout, ntw) : 1;
+  if (pick < 0) return pick;
+  // the pipelined kernels address input rows with 32-bit byte offsets (an input has at most 8x the output's rows)
+  if (packed && (int64_t)num_out * 8 * ld_in * 4 >= (1ll << 32)) return MOPA_ERR_ARG;
+  const bool flag = (pick & SPK_FLAG) != 0;
+  int osplit = SPK_OSPLIT(pick);   // (chosen for the stated size; the partial copies are of the real one)
   if (osplit > 1 && ws_bytes < (size_t)osplit * num_out * cout * sizeof(float)) osplit = 1;
   float* part = (float*)ws;
-#define GO(N) return dispatch_blk_c<N>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, aligned, part, osplit, st)
-  switch (ntw) {
-    case 1: GO(1);
-    case 2: GO(2);
-    default: GO(4);
+  switch (SPK_KERNEL(pick)) {
+#ifdef MOPA_EXP_RING
+    case SPK(SPK_RING, 1, 0, 0, 0): case SPK(SPK_RING, 2, 0, 0, 0): case SPK(SPK_RING, 3, 0, 0, 0): case SPK(SPK_RING, 4, 0, 0, 0):
+      return mopa_ring_launch(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, SPK_NTW(pick), st);
+#endif
+#define PP(N, DD, MU) case SPK(SPK_PIPE, N, 0, DD, 0): return launch_pipe<N, DD, MU>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, w_flip, out, ld_out, st);
+    PP(1, 2, 40) PP(2, 6, 32) PP(3, 6, 40) PP(4, 4, 28)
+#undef PP
+#define T4(N, KU, DD, WV) case SPK(SPK_T4, N, KU, DD, WV): return launch_t4<N, KU, DD, WV>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, flag, st);
+    T4(1, 1, 2, 1) T4(1, 2, 2, 1) T4(1, 3, 2, 1) T4(1, 4, 2, 1) T4(2, 1, 2, 1) T4(2, 2, 2, 1) T4(2, 3, 2, 1) T4(2, 4, 2, 1)
+    T4(3, 1, 2, 1) T4(3, 2, 2, 1) T4(3, 3, 2, 1)
+    T4(1, 1, 4, 4) T4(1, 2, 2, 4) T4(1, 5, 2, 4) T4(1, 7, 2, 4) T4(1, 3, 2, 4) T4(1, 4, 2, 4)
+    T4(2, 1, 2, 4) T4(2, 2, 2, 4) T4(2, 5, 2, 4) T4(2, 3, 2, 4) T4(2, 4, 2, 4)
+    T4(3, 1, 2, 4) T4(3, 2, 2, 4) T4(3, 3, 2, 4)
+#undef T4
+#define RB(N, C) case SPK(SPK_BLK, N, C, 0, 0): return launch_blk<N, C>(grp_start, grp_o, grp_in, grp_out, K, num_out, in, ld_in, cin, weight, cout, w_flip, out, ld_out, flag, part, osplit, st);
+#define RBN(N) RB(N, 1) RB(N, 2) RB(N, 3) RB(N, 4) RB(N, 8) RB(N, 12)
+    RBN(1) RBN(2) RBN(4)
+#undef RBN
+#undef RB
+    default: return MOPA_ERR_ARG;
   }
-#undef GO
+}
+
+// The kernel a forward launch would run, without launching: entry 0 = mopa_spconv_fwd, 1 = mopa_spconv_fwd_grouped, 2 =
+// mopa_spconv_fwd_run, on a table of `rows` rows (or of the size stated in bits 8-30 of w_flip) with 16-byte-aligned pointers and an
+// output stride of whole float4; has_ws: a sufficient workspace is passed.  -> the SPK value of sprun_pack.h, or the error the entry
+// point would return for the shape.  Host only.
+MOPA_API int mopa_spconv_fwd_kernel(int32_t entry, int32_t K, int32_t rows, int32_t cin, int32_t cout, int32_t ld_in, int32_t w_flip,
+                                    int32_t has_ws, int32_t one_rule_per_row) {
+  if (K <= 0 || K > 27 || rows <= 0 || cin <= 0 || cout <= 0 || ld_in < cin) return MOPA_ERR_ARG;
+  const bool aligned = cin % 16 == 0 && cout % 16 == 0 && ld_in % 4 == 0;
+  const int64_t stated = spk_stated_rows(w_flip, rows);
+  switch (entry) {
+    case 0: return cin > 192 ? MOPA_ERR_ARG : pick_fwd(K, stated, cin, cout, aligned, true);
+    case 1: return cin > ((w_flip & 2) ? 224 : 192) ? MOPA_ERR_ARG : pick_grouped(K, stated, cin, cout, (w_flip >> 1) & 1, aligned, has_ws != 0);
+    case 2: return ld_in % 4 ? MOPA_ERR_ARG : (one_rule_per_row || has_ws) ? spk_pick_run(K, stated, cin, cout, one_rule_per_row) : MOPA_ERR_WORKSPACE;
+    default: return MOPA_ERR_ARG;
+  }
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -416,7 +416,7 @@ static int launch_run(const int* hdr, const int* run_in, const int* run_out, int
 }
 
 // Same contract as mopa_spconv_fwd on the table whose run-major rulebook is `runs` (mopa_rulebook_runs_build_batched), with the
-// weight in the run layout (mopa_spconv_run_pack_weight; w_flip bit 0 = mirrored filter offsets).  one_rule_per_row: 1 = every
+// weight in the run layout (mopa_spconv_run_pack_weight; w_flip bit 0 = mirrored filter offsets, bits 8-30: sprun_pack.h).  one_rule_per_row: 1 = every
 // output row has exactly one rule (Deconvolution k2s2, backward-data of Convolution k2s2: every fine row has one parent), 2 = at
 // most one (rows without a rule are zeroed first): products go straight to `out`, no slab.  0: ws = the slab,
 // mopa_spconv_run_workspace_bytes.
@@ -424,8 +424,8 @@ MOPA_API int mopa_spconv_fwd_run(const int32_t* runs, int32_t K, int32_t num_out
                                  const float* weight_run, int32_t cout, int32_t w_flip, float* out, int32_t ld_out,
                                  int32_t one_rule_per_row, void* ws, size_t ws_bytes, void* stream) {
   if (!runs || !in || !weight_run || !out || K <= 0 || K > 27 || num_out <= 0 || ld_in < cin || ld_out < cout) return MOPA_ERR_ARG;
-  const int nt = run_nt(cin, cout);
-  if (nt == 0 || ld_in % 4 || ld_out % 4 || (((uintptr_t)in | (uintptr_t)out | (uintptr_t)weight_run) & 15)) return MOPA_ERR_ARG;
+  const int pick = spk_pick_run(K, spk_stated_rows(w_flip, num_out), cin, cout, one_rule_per_row);   // (sprun_pack.h)
+  if (pick < 0 || ld_in % 4 || ld_out % 4 || (((uintptr_t)in | (uintptr_t)out | (uintptr_t)weight_run) & 15)) return MOPA_ERR_ARG;
   if ((int64_t)num_out * 8 * ld_in * 4 >= (1ll << 32)) return MOPA_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int64_t cap = run_cap(K, num_out);
@@ -442,24 +442,15 @@ MOPA_API int mopa_spconv_fwd_run(const int32_t* runs, int32_t K, int32_t num_out
   } else if (one_rule_per_row != 1 && hipMemset2DAsync(out, (size_t)ld_out * 4, 0, (size_t)cout * 4, (size_t)num_out, st) != hipSuccess) {
     return MOPA_ERR_LAUNCH;
   }
-  // items of 128 slots (two row groups per wave) unless the table is so short that they would leave CUs idle: the rule count is
-  // not known on the host (no synchronisation), ~9 rules per row on the deep 27-offset tables, rows_in <= 8 rows_out otherwise
-  const int64_t rules_est = K == 27 ? (int64_t)9 * num_out : one_rule_per_row ? num_out : (int64_t)5 * num_out / 2;
-  const int rg = rules_est / 128 < 1024 ? 1 : 2;   // (fewer than ~4 items of 128 per CU: level 5 at 8 scans 27 -> 17 us with 64-slot items)
   int rc;
-#define RUN_L(N, G) rc = launch_run<N, G>(hdr, run_in, run_out, K, cap, in, ld_in, cin, weight_run, cout, w_flip & 1, dst, ld_dst, one_rule_per_row != 0, st)
-#define RUN_N(N) if (rg == 1) RUN_L(N, 1); else RUN_L(N, 2);
-  switch (nt) {
-    case 1: RUN_N(1); break;
-    case 2: RUN_N(2); break;
-    case 3: RUN_N(3); break;
-    case 4: RUN_N(4); break;
-    case 5: RUN_N(5); break;
-    case 6: RUN_N(6); break;
-    default: RUN_N(7); break;
-  }
+  switch (SPK_KERNEL(pick) | SPK_RG(pick) << 24) {
+#define RUN_L(N, G) case SPK(SPK_RUN, N, 0, 0, 0) | G << 24: rc = launch_run<N, G>(hdr, run_in, run_out, K, cap, in, ld_in, cin, weight_run, cout, w_flip & 1, dst, ld_dst, (pick & SPK_FLAG) != 0, st); break;
+#define RUN_N(N) RUN_L(N, 1) RUN_L(N, 2)
+    RUN_N(1) RUN_N(2) RUN_N(3) RUN_N(4) RUN_N(5) RUN_N(6) RUN_N(7)
 #undef RUN_N
 #undef RUN_L
+    default: return MOPA_ERR_ARG;
+  }
   if (rc) return rc;
   if (!one_rule_per_row) {
     k_run_reduce<<<(unsigned)cdiv64(num_out, RED_ROWS), 256, 0, st>>>(pos, K, num_out, (const float*)ws, cout, out, ld_out);

@@ -29,3 +29,39 @@ static inline int run_nt(int cin, int cout) {
     if (tiles % c == 0) return c;
   return 0;
 }
+
+// ---- which kernel a forward launch runs (mopa_spconv_fwd, mopa_spconv_fwd_grouped, mopa_spconv_fwd_run), as ONE value: each entry
+// point computes it in one host function (pick_fwd / pick_grouped / pick_run), its launcher is a switch over it, and
+// mopa_spconv_fwd_kernel returns it to a caller that only asks.  Fields:
+//   bits 0-3   family (SPK_*)
+//   bits 4-7   NTW: 16-column tiles per column group (k_spconv_run: NT; k_spconv_stem: CIN)
+//   bits 8-11  NA (k_spconv_fwd, k_spconv_blk), NKU (k_spconv_t4), COUT / 16 (k_spconv_stem)
+//   bits 12-15 D: depth of the load ring (k_spconv_pipe, k_spconv_t4)
+//   bits 16-18 NWV: waves per tile (k_spconv_t4)
+//   bit  19    ALIGNED (k_spconv_fwd, k_spconv_blk), PART (k_spconv_t4), SCATTER (k_spconv_run)
+//   bits 20-23 osplit (k_spconv_blk: blocks over the filter offsets, 1 = no partial copies)
+//   bits 24-25 RG (k_spconv_run)
+enum { SPK_STEM = 1, SPK_FWD = 2, SPK_BLK = 3, SPK_PIPE = 4, SPK_T4 = 5, SPK_RUN = 6, SPK_RING = 7 };
+#define SPK(fam, ntw, nk, d, nwv) ((fam) | (ntw) << 4 | (nk) << 8 | (d) << 12 | (nwv) << 16)
+#define SPK_KERNEL(p) ((p) & 0x7ffff)        // what the launcher switches over: the template arguments that are not a bool
+#define SPK_FAMILY(p) ((p) & 15)
+#define SPK_NTW(p) (((p) >> 4) & 15)
+#define SPK_FLAG (1 << 19)
+#define SPK_OSPLIT(p) (((p) >> 20) & 15)
+#define SPK_RG(p) (((p) >> 24) & 3)
+// w_flip of the three entry points: bit 0 mirrored offsets, bit 1 packed weights (grouped call), bits 8-30 "decide as if the table
+// had this many 64-row tiles" (0: the real row count).  The kernel runs on the real table; only the choice above uses the stated size.
+static inline int64_t spk_stated_rows(int w_flip, int64_t num_out) {
+  const int64_t tiles = (w_flip >> 8) & 0x7fffff;
+  return tiles ? tiles * 64 : num_out;
+}
+// Which k_spconv_run mopa_spconv_fwd_run launches on a table of `rows` rows (-1: shape not supported).  Items of 128 slots (two row
+// groups per wave) unless the table is so short that they would leave CUs idle: the rule count is not known on the host (no
+// synchronisation), ~9 rules per row on the deep 27-offset tables, rows_in <= 8 rows_out otherwise.
+static inline int spk_pick_run(int K, int64_t rows, int cin, int cout, int one_rule_per_row) {
+  const int nt = run_nt(cin, cout);
+  if (nt == 0) return -1;
+  const int64_t rules_est = K == 27 ? 9 * rows : one_rule_per_row ? rows : 5 * rows / 2;
+  const int rg = rules_est / 128 < 1024 ? 1 : 2;   // (fewer than ~4 items of 128 per CU: level 5 at 8 scans 27 -> 17 us with 64-slot items)
+  return SPK(SPK_RUN, nt, 0, 0, 0) | (one_rule_per_row ? SPK_FLAG : 0) | rg << 24;
+}
