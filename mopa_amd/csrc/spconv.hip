@@ -1612,7 +1612,10 @@ __global__ __launch_bounds__(256) void k_spconv_stem_wgrad(const int* __restrict
   }
 }
 
-static void wgrad_plan(int K, int A_out, int cin, int cout, int* mu, int* mblocks, int* nchunks, int* rows_per_chunk) {
+// `stated`: the table size the size-dependent choices follow (sprun_pack.h; = A_out unless the caller states one) -- the wave target
+// here and, through *stated_grid (the grid a table of that size would get), the four-waves-per-block form in pick_wgrad.
+static void wgrad_plan(int K, int64_t A_out, int64_t stated, int cin, int cout, int* mu, int* mblocks, int* nchunks, int* rows_per_chunk,
+                       int64_t* stated_grid) {
   const int mt = (cin + 15) / 16;
   int m = 1;
   for (int c = 4; c >= 1; --c)
@@ -1627,17 +1630,22 @@ static void wgrad_plan(int K, int A_out, int cin, int cout, int* mu, int* mblock
   // scanned entries) were 1.4-2x slower at the old 16384 than at 512, the 27-offset tables 5-15 % -- while the simple kernel of
   // the unaligned shapes hides its dependent ballot / gather chain by wave count only (16384).
   const bool pipelined = cin % 16 == 0 && cout % 16 == 0;
-  const int waves = !pipelined ? 16384 : K != 27 ? 512 : cout <= 16 ? 4096 : A_out < 4096 ? 512 : 2048;
-  int64_t nc = cdiv64(waves, per);
-  const int64_t max_rows = cdiv64(A_out, 256);
+  const int waves = !pipelined ? 16384 : K != 27 ? 512 : cout <= 16 ? 4096 : stated < 4096 ? 512 : 2048;
   const int64_t max_slab = (32ll << 20) / ((int64_t)K * cin * cout * 4) + 1;
-  if (nc > max_rows) nc = max_rows;
-  if (nc > max_slab) nc = max_slab;
-  if (nc > 2048) nc = 2048;
-  if (nc < 1) nc = 1;
-  int rpc = (int)cdiv64(cdiv64(A_out, nc), 64) * 64;
-  *nchunks = (int)cdiv64(A_out, rpc);
-  *rows_per_chunk = rpc;
+  auto chunks = [&](int64_t rows, int* rpc_out) {
+    int64_t nc = cdiv64(waves, per);
+    const int64_t max_rows = cdiv64(rows, 256);
+    if (nc > max_rows) nc = max_rows;
+    if (nc > max_slab) nc = max_slab;
+    if (nc > 2048) nc = 2048;
+    if (nc < 1) nc = 1;
+    const int rpc = (int)cdiv64(cdiv64(rows, nc), 64) * 64;
+    *rpc_out = rpc;
+    return cdiv64(rows, rpc);
+  };
+  *nchunks = (int)chunks(A_out, rows_per_chunk);
+  int rpc_stated;
+  *stated_grid = (int64_t)K * (stated == A_out ? *nchunks : chunks(stated, &rpc_stated)) * (*mblocks);
 }
 
 static inline bool stem_wgrad_shape(int K, int cin, int cout) { return K <= 27 && cin == 1 && cout == 16; }   // (7 x 16 accumulators per lane)
@@ -1647,83 +1655,123 @@ static inline int stem_wgrad_blocks(int A_out, int* rows_per_block) {
   *rows_per_block = (int)cdiv64(cdiv64(A_out, nb), 64) * 64;
   return (int)cdiv64(A_out, *rows_per_block);
 }
-MOPA_API size_t mopa_spconv_wgrad_workspace_bytes(int32_t K, int32_t num_out, int32_t cin, int32_t cout) {
-  size_t stem = 0;
-  if (stem_wgrad_shape(K, cin, cout)) {   // (the generic plan's size as well: an unaligned output gradient takes that path)
-    int rpb;
-    stem = align_up((size_t)stem_wgrad_blocks(num_out, &rpb) * K * cin * cout * sizeof(float), 256);
-  }
-  int mu, mb, nc, rpc;
-  wgrad_plan(K, num_out, cin, cout, &mu, &mb, &nc, &rpc);
-  const size_t gen = align_up((size_t)nc * K * cin * cout * sizeof(float), 256);
-  return gen > stem ? gen : stem;
+static inline bool stem_wgrad_on() {   // A/B switch
+  static const int on = getenv("MOPA_SPCONV_STEM") ? atoi(getenv("MOPA_SPCONV_STEM")) : 1;
+  return on != 0;
 }
 
-template <int MU>
-static int launch_wgrad(int nt, dim3 grid, hipStream_t st, const int* nbr, int A_out, int rpc, const float* in,
-                        int ld_in, int cin, const float* dout, int ld_do, int cout, float* slabs, int K, bool aligned) {
-  constexpr int DD = MU <= 2 ? 8 : 6;
-  if (aligned) {
-    // (almost) the whole grid resident at once: split every wave four ways -- unless the combine buffer would leave
-    // only two blocks per CU (measured: 128->64 at level 3 190 -> 134 us, 96->48 154 -> 125; 64->96 80 -> 97 without the cap)
-    const bool four = (int64_t)grid.x * grid.y * grid.z <= 4200 && MU * nt <= 16;
-    switch (nt) {
-#define CASE(N) case N: if (four) k_spconv_wgrad2<MU, N, (MU + N <= 6 ? 8 : DD), 4><<<grid, 256, 4 * 2 * (WG2_CAP + 64) * 4 + MU * N * 4 * 64 * 4, st>>>(nbr, A_out, rpc, in, ld_in, cin, dout, ld_do, cout, slabs, K); \
-                else k_spconv_wgrad2<MU, N, (MU + N <= 6 ? 8 : DD), 1><<<grid, 64, 2 * (WG2_CAP + 64) * 4 + MU * N * 4 * 64 * 4, st>>>(nbr, A_out, rpc, in, ld_in, cin, dout, ld_do, cout, slabs, K); break
-      CASE(1); CASE(2); CASE(3); CASE(4); CASE(5); CASE(6); CASE(7);
-#undef CASE
-      default: return MOPA_ERR_ARG;
-    }
-    return hipGetLastError() == hipSuccess ? MOPA_OK : MOPA_ERR_LAUNCH;
+// Everything about one mopa_spconv_bwd_weight launch, decided HERE and nowhere else: the packed instantiation (sprun_pack.h WGK),
+// its grid (K x nchunks x mblocks; the stem: nchunks blocks of rpc rows), LDS bytes and the workspace the call asks for.
+struct WgPick { int pick, mblocks, nchunks, rpc; size_t ws_bytes, lds; };
+constexpr int wg2_depth(int mu, int nt) { return mu + nt <= 6 ? 8 : mu <= 2 ? 8 : 6; }
+// in_low / dout_low: the low four address bits of the two operands.  -> MOPA_OK or the entry point's refusal.
+static int pick_wgrad(int K, int64_t A_out, int64_t stated, int cin, int cout, int ld_in, int ld_dout, unsigned in_low, unsigned dout_low,
+                      WgPick* p) {
+  if (K <= 0 || A_out <= 0 || A_out > INT32_MAX || cin <= 0 || cout <= 0 || cout > 112 || ld_in < cin || ld_dout < cout) return MOPA_ERR_ARG;
+  int mu, mb, nc, rpc;
+  int64_t stated_grid;
+  wgrad_plan(K, A_out, stated, cin, cout, &mu, &mb, &nc, &rpc, &stated_grid);
+  const size_t gen = align_up((size_t)nc * K * cin * cout * sizeof(float), 256);
+  const bool stem_shape = stem_wgrad_shape(K, cin, cout);
+  int rpb = 0;
+  const int nb = stem_shape ? stem_wgrad_blocks((int)A_out, &rpb) : 0;
+  const size_t stem = stem_shape ? align_up((size_t)nb * K * cin * cout * sizeof(float), 256) : 0;
+  p->ws_bytes = gen > stem ? gen : stem;   // (a stem shape asks for both plans' size: an unaligned output gradient takes the generic one)
+  if (stem_shape && stem_wgrad_on() && ld_dout % 4 == 0 && dout_low == 0) {
+    *p = WgPick{WGK(WGK_STEM, 0, 1, 0, 0), 1, nb, rpb, p->ws_bytes, 0};
+    return MOPA_OK;
   }
-  switch (nt) {
-#define CASE(N) case N: k_spconv_wgrad<MU, N><<<grid, 64, 0, st>>>(nbr, A_out, rpc, in, ld_in, cin, dout, ld_do, cout, slabs, K); break
-    CASE(1); CASE(2); CASE(3); CASE(4); CASE(5); CASE(6); CASE(7);
-#undef CASE
+  const int nt = (cout + 15) / 16;
+  // pipelined kernel: whole 16-channel tiles, 32-bit element offsets (row * ld < 2^32) and 4-byte aligned rows
+  const bool aligned = cin % 16 == 0 && cout % 16 == 0 && A_out * ld_dout < (1ll << 32) && A_out * 8 * ld_in < (1ll << 32) &&
+                       ((in_low | dout_low) & 3) == 0;
+  p->mblocks = mb;
+  p->nchunks = nc;
+  p->rpc = rpc;
+  if (!aligned) {
+    p->pick = WGK(WGK_SIMPLE, mu, nt, 0, 0);
+    p->lds = 0;
+    return MOPA_OK;
+  }
+  // (almost) the whole grid resident at once: split every wave four ways -- unless the combine buffer would leave
+  // only two blocks per CU (measured: 128->64 at level 3 190 -> 134 us, 96->48 154 -> 125; 64->96 80 -> 97 without the cap)
+  const int nwv = stated_grid <= 4200 && mu * nt <= 16 ? 4 : 1;
+  p->pick = WGK(WGK_PIPE, mu, nt, wg2_depth(mu, nt), nwv);
+  p->lds = (size_t)nwv * 2 * (WG2_CAP + 64) * 4 + (size_t)mu * nt * 4 * 64 * 4;
+  return MOPA_OK;
+}
+
+MOPA_API size_t mopa_spconv_wgrad_workspace_bytes(int32_t K, int32_t num_out, int32_t cin, int32_t cout) {
+  WgPick p;   // (alignment facts do not move the size)
+  return pick_wgrad(K, num_out, num_out, cin, cout, cin, cout, 0, 0, &p) == MOPA_OK ? p.ws_bytes : 0;
+}
+
+static int launch_wgrad(const WgPick& p, hipStream_t st, const int* nbr, int K, int A_out, const float* in, int ld_in, int cin,
+                        const float* dout, int ld_do, int cout, float* slabs) {
+  const dim3 grid(K, p.nchunks, p.mblocks);
+  switch (p.pick) {
+    case WGK(WGK_STEM, 0, 1, 0, 0): k_spconv_stem_wgrad<16><<<p.nchunks, 256, 0, st>>>(nbr, K, A_out, p.rpc, in, ld_in, dout, ld_do, slabs); break;
+#define WG(MU, N)                                                                                                                          \
+    case WGK(WGK_SIMPLE, MU, N, 0, 0): k_spconv_wgrad<MU, N><<<grid, 64, 0, st>>>(nbr, A_out, p.rpc, in, ld_in, cin, dout, ld_do, cout, slabs, K); break; \
+    case WGK(WGK_PIPE, MU, N, wg2_depth(MU, N), 1):                                                                                        \
+      k_spconv_wgrad2<MU, N, wg2_depth(MU, N), 1><<<grid, 64, p.lds, st>>>(nbr, A_out, p.rpc, in, ld_in, cin, dout, ld_do, cout, slabs, K); break; \
+    case WGK(WGK_PIPE, MU, N, wg2_depth(MU, N), 4):                                                                                        \
+      k_spconv_wgrad2<MU, N, wg2_depth(MU, N), 4><<<grid, 256, p.lds, st>>>(nbr, A_out, p.rpc, in, ld_in, cin, dout, ld_do, cout, slabs, K); break;
+#define WGM(MU) WG(MU, 1) WG(MU, 2) WG(MU, 3) WG(MU, 4) WG(MU, 5) WG(MU, 6) WG(MU, 7)
+    WGM(1) WGM(2) WGM(3) WGM(4)
+#undef WGM
+#undef WG
     default: return MOPA_ERR_ARG;
   }
   return hipGetLastError() == hipSuccess ? MOPA_OK : MOPA_ERR_LAUNCH;
 }
 
-// dW[K][cin][cout] (+= if accumulate) from in[*, cin] and dout[num_out, cout] over the rules of nbr[K][num_out].
+// dW[K][cin][cout] (+= if accumulate & 1) from in[*, cin] and dout[num_out, cout] over the rules of nbr[K][num_out]; accumulate bits
+// 8-30: see sprun_pack.h.  ws >= what mopa_spconv_wgrad_kernel reports for the same arguments (without a stated size:
+// mopa_spconv_wgrad_workspace_bytes).
 MOPA_API int mopa_spconv_bwd_weight(const int32_t* nbr, int32_t K, int32_t num_out, const float* in, int32_t ld_in,
                                     int32_t cin, const float* dout, int32_t ld_dout, int32_t cout, float* dweight,
                                     int32_t accumulate, void* ws, size_t ws_bytes, void* stream) {
-  if (K <= 0 || num_out <= 0 || cin <= 0 || cout <= 0 || cout > 112 || ld_in < cin || ld_dout < cout) return MOPA_ERR_ARG;
-  if (ws_bytes < mopa_spconv_wgrad_workspace_bytes(K, num_out, cin, cout)) return MOPA_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  static const int stem_on = getenv("MOPA_SPCONV_STEM") ? atoi(getenv("MOPA_SPCONV_STEM")) : 1;   // A/B switch (must match the workspace query)
-  if (stem_wgrad_shape(K, cin, cout) && stem_on && ld_dout % 4 == 0 && ((uintptr_t)dout & 15) == 0) {
-    int rpb;
-    const int nb = stem_wgrad_blocks(num_out, &rpb);
-    float* sl = (float*)ws;
-#define STEM_WG() k_spconv_stem_wgrad<16><<<nb, 256, 0, st>>>(nbr, K, num_out, rpb, in, ld_in, dout, ld_dout, sl)
-    STEM_WG();
-#undef STEM_WG
-    MOPA_CHECK_LAUNCH();
-    const int64_t n = (int64_t)K * cin * cout;
-    k_reduce_slabs<<<(unsigned)cdiv64(n, 16), 256, 0, st>>>(sl, nb, n, dweight, accumulate);
-    MOPA_CHECK_LAUNCH();
-    return MOPA_OK;
-  }
-  int mu, mb, nc, rpc;
-  wgrad_plan(K, num_out, cin, cout, &mu, &mb, &nc, &rpc);
-  dim3 grid(K, nc, mb);
-  float* slabs = (float*)ws;
-  const int nt = (cout + 15) / 16;
-  // pipelined kernel: whole 16-channel tiles, 32-bit element offsets (row * ld < 2^32) and 4-byte aligned rows
-  const bool aligned = cin % 16 == 0 && cout % 16 == 0 && (int64_t)num_out * ld_dout < (1ll << 32) &&
-                       (int64_t)num_out * 8 * ld_in < (1ll << 32) && (((uintptr_t)in | (uintptr_t)dout) & 3) == 0;
-  int rc;
-  switch (mu) {
-    case 1: rc = launch_wgrad<1>(nt, grid, st, nbr, num_out, rpc, in, ld_in, cin, dout, ld_dout, cout, slabs, K, aligned); break;
-    case 2: rc = launch_wgrad<2>(nt, grid, st, nbr, num_out, rpc, in, ld_in, cin, dout, ld_dout, cout, slabs, K, aligned); break;
-    case 3: rc = launch_wgrad<3>(nt, grid, st, nbr, num_out, rpc, in, ld_in, cin, dout, ld_dout, cout, slabs, K, aligned); break;
-    default: rc = launch_wgrad<4>(nt, grid, st, nbr, num_out, rpc, in, ld_in, cin, dout, ld_dout, cout, slabs, K, aligned); break;
-  }
+  WgPick p;
+  const int rc = pick_wgrad(K, num_out, spk_stated_rows(accumulate, num_out), cin, cout, ld_in, ld_dout, (unsigned)((uintptr_t)in & 15),
+                            (unsigned)((uintptr_t)dout & 15), &p);
   if (rc) return rc;
+  if (ws_bytes < p.ws_bytes) return MOPA_ERR_WORKSPACE;
+  accumulate &= 1;
+  hipStream_t st = (hipStream_t)stream;
+  float* slabs = (float*)ws;
+  const int lrc = launch_wgrad(p, st, nbr, K, num_out, in, ld_in, cin, dout, ld_dout, cout, slabs);
+  if (lrc) return lrc;
   const int64_t n = (int64_t)K * cin * cout;
-  k_reduce_slabs<<<(unsigned)cdiv64(n, 16), 256, 0, st>>>(slabs, nc, n, dweight, accumulate);
+  k_reduce_slabs<<<(unsigned)cdiv64(n, 16), 256, 0, st>>>(slabs, p.nchunks, n, dweight, accumulate);
   MOPA_CHECK_LAUNCH();
   return MOPA_OK;
+}
+
+// Which kernel mopa_spconv_bwd_weight (entry 0) or mopa_spconv_bwd_weight_run (entry 1) would launch for these arguments, without
+// launching: the packed value of sprun_pack.h (WGK), or the error the entry point would return for them (a short workspace aside:
+// the size it asks for is reported).  rows: the table's real row count; accumulate: as in the call (bits 8-30 state a size);
+// ptr_low: the low four address bits of in (bits 0-3), dout (bits 4-7) and ws (bits 8-11); info_host (8 x int64, may be null):
+// chunk count, rows per chunk (table entry), piece size S, piece count (run entry), workspace bytes, LDS bytes, blocks of the grid, 0 (reserved).
+MOPA_API int mopa_spconv_wgrad_kernel(int32_t entry, int32_t K, int32_t rows, int32_t cin, int32_t cout, int32_t ld_in, int32_t ld_dout,
+                                      int32_t accumulate, int32_t ptr_low, int64_t* info_host, int32_t one_rule_per_row) {
+  int64_t info[WGI_N] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int rc = MOPA_ERR_ARG;
+  if (entry == 0) {
+    WgPick p;
+    rc = pick_wgrad(K, rows, spk_stated_rows(accumulate, rows), cin, cout, ld_in, ld_dout, ptr_low & 15, (ptr_low >> 4) & 15, &p);
+    if (rc == MOPA_OK) {
+      rc = p.pick;
+      info[WGI_CHUNKS] = p.nchunks;
+      info[WGI_ROWS_PER_CHUNK] = p.rpc;
+      info[WGI_WS_BYTES] = (int64_t)p.ws_bytes;
+      info[WGI_LDS_BYTES] = (int64_t)p.lds;
+      info[WGI_BLOCKS] = (p.pick & 15) == WGK_STEM ? p.nchunks : (int64_t)K * p.nchunks * p.mblocks;
+    }
+  } else if (entry == 1) {
+    rc = mopa_wgr_pick_for_query(K, rows, spk_stated_rows(accumulate, rows), cin, cout, one_rule_per_row, ld_in, ld_dout, (unsigned)ptr_low, info);
+  }
+  if (info_host)
+    for (int i = 0; i < WGI_N; ++i) info_host[i] = rc > 0 ? info[i] : 0;
+  return rc;
 }

@@ -737,12 +737,16 @@ static inline int wgr_stride(int c, int n16) {   // smallest row stride >= c wit
   while ((s & 63) != want) s += 4;
   return s;
 }
-struct WgrPlan { int mu, nt, S, sA, sB; int64_t npieces; size_t lds; };
-static inline bool wgr_plan(int K, int64_t num_out, int cin, int cout, int one_rule_per_row, WgrPlan* p) {
+// Everything about one mopa_spconv_bwd_weight_run launch: the packed instantiation (sprun_pack.h WGK), piece size and count, LDS.
+struct WgrPlan { int pick, mu, nt, S, sA, sB; int64_t npieces; size_t lds; };
+// `stated`: the table size the piece size follows (sprun_pack.h; = num_out unless the caller states one); the bound on the slots, the
+// slab cap and with them the piece count stay on the real table.
+static inline bool wgr_plan(int K, int64_t num_out, int64_t stated, int cin, int cout, int one_rule_per_row, WgrPlan* p) {
   if (K <= 0 || K > 27 || cin < 16 || cin > 256 || cin % 16 || cout < 16 || cout > 112 || cout % 16) return false;
   const int cinb = cin / 16;
   p->mu = (cinb + 3) / 4;
   p->nt = cout / 16;
+  p->pick = WGK(WGK_RUN, p->mu, p->nt, 0, 0);
   p->sA = wgr_stride(cin, p->mu);
   p->sB = wgr_stride(cout, p->nt);
   p->lds = (size_t)2 * WGR_TS * (p->sA + p->sB) * sizeof(float) + 512 * 16;   // two tiles of each operand + the dummy slots
@@ -754,7 +758,7 @@ static inline bool wgr_plan(int K, int64_t num_out, int cin, int cout, int one_r
   // row on the 27-offset tables); the 8-offset tables (one rule per row, small slabs): three pieces per CU, from 128 slots.  And no
   // more slab than 128 MiB at the BOUND on the slots.
   const int ncu = mopa_cu_count() > 0 ? mopa_cu_count() : 256;
-  const int64_t rules_est = one_rule_per_row ? num_out : K == 27 ? 9 * num_out : 5 * num_out / 2;
+  const int64_t rules_est = one_rule_per_row ? stated : K == 27 ? 9 * stated : 5 * stated / 2;
   int64_t S = one_rule_per_row ? rules_est / (3 * ncu) : (int64_t)(1.2 * sqrt((double)rules_est));
   S = (S + WGR_TS - 1) / WGR_TS * WGR_TS;
   if (S < 128) S = 128;
@@ -766,6 +770,26 @@ static inline bool wgr_plan(int K, int64_t num_out, int cin, int cout, int one_r
   p->npieces = bound / S + K;
   return true;
 }
+static inline size_t wgr_ws_bytes(const WgrPlan& p, int cin, int cout) { return align_up((size_t)p.npieces * cin * cout * sizeof(float), 256); }
+// The entry point's decision and its refusals of a shape (ptr_low: the low four address bits of in, dout and ws in bits 0-3, 4-7, 8-11).
+static int wgr_pick(int K, int64_t num_out, int64_t stated, int cin, int cout, int one_rule_per_row, int ld_in, int ld_dout, unsigned ptr_low,
+                    WgrPlan* p) {
+  if (num_out <= 0 || !wgr_plan(K, num_out, stated, cin, cout, one_rule_per_row, p)) return MOPA_ERR_ARG;
+  if (ld_in < cin || ld_dout < cout || (ld_in & 3) || (ld_dout & 3) || (ptr_low & 0xfff)) return MOPA_ERR_ARG;
+  return MOPA_OK;
+}
+int mopa_wgr_pick_for_query(int K, int64_t num_out, int64_t stated, int cin, int cout, int one_rule_per_row, int ld_in, int ld_dout,
+                            unsigned ptr_low, int64_t* info) {
+  WgrPlan p;
+  const int rc = wgr_pick(K, num_out, stated, cin, cout, one_rule_per_row, ld_in, ld_dout, ptr_low, &p);
+  if (rc) return rc;
+  info[WGI_S] = p.S;
+  info[WGI_PIECES] = p.npieces;
+  info[WGI_WS_BYTES] = (int64_t)wgr_ws_bytes(p, cin, cout);
+  info[WGI_LDS_BYTES] = (int64_t)p.lds;
+  info[WGI_BLOCKS] = p.npieces;
+  return p.pick;
+}
 // Which weight gradients take the run lists (profiles/r5_wgrad_run.md: us per launch of both kernels at 8 and 16 scans, every layer
 // shape): the 27-offset layers from 48 input channels on (below, the old kernel's one-wave-per-(offset, chunk) walk is as fast: the
 // GEMM is small against the table scan either way) up to 192 (224: 94 KB of LDS tiles, one block per CU) -- unless more than 30 % of
@@ -774,7 +798,7 @@ static inline bool wgr_plan(int K, int64_t num_out, int cin, int cout, int one_r
 MOPA_API int mopa_spconv_wgrad_run_wanted(int32_t K, int32_t num_out, int32_t cin, int32_t cout, int32_t one_rule_per_row) {
   static const int mode = getenv("MOPA_SPCONV_WGRAD_RUN") ? atoi(getenv("MOPA_SPCONV_WGRAD_RUN")) : 1;
   WgrPlan p;
-  if (!mode || !wgr_plan(K, num_out, cin, cout, one_rule_per_row, &p)) return 0;
+  if (!mode || !wgr_plan(K, num_out, num_out, cin, cout, one_rule_per_row, &p)) return 0;
   if (mode == 2) return 1;
   if (one_rule_per_row) return num_out >= 40000 && (cin >= 48 || cout >= 48);
   if (K != 27 || cin < 48 || cin > 192) return 0;
@@ -783,40 +807,40 @@ MOPA_API int mopa_spconv_wgrad_run_wanted(int32_t K, int32_t num_out, int32_t ci
 }
 MOPA_API size_t mopa_spconv_wgrad_run_workspace_bytes(int32_t K, int32_t num_out, int32_t cin, int32_t cout, int32_t one_rule_per_row) {
   WgrPlan p;
-  if (!wgr_plan(K, num_out, cin, cout, one_rule_per_row, &p)) return 0;
-  return align_up((size_t)p.npieces * cin * cout * sizeof(float), 256);
+  if (!wgr_plan(K, num_out, num_out, cin, cout, one_rule_per_row, &p)) return 0;
+  return wgr_ws_bytes(p, cin, cout);
 }
 
-template <int MU>
+template <int MU, int NT>
 static int launch_wgrad_run(const WgrPlan& p, const int* hdr, const int* ia, const int* ib, int K, const float* A, int ldA, int cin, const float* B,
                             int ldB, int cout, float* slabs, hipStream_t st) {
-  typedef void (*kern_t)(const int*, const int*, const int*, int, int, const float*, int, int, const float*, int, int, int, int, float*);
-  static const kern_t kerns[7] = {k_wgrad_run<MU, 1>, k_wgrad_run<MU, 2>, k_wgrad_run<MU, 3>, k_wgrad_run<MU, 4>,
-                                  k_wgrad_run<MU, 5>, k_wgrad_run<MU, 6>, k_wgrad_run<MU, 7>};
-  static std::atomic<bool> attr[64][7];
+  static std::atomic<bool> attr[64];
   const int dev = mopa_device_index();
   if (dev < 0) return MOPA_ERR_LAUNCH;
-  const kern_t k = kerns[p.nt - 1];
-  if (p.lds > 64 * 1024 && !attr[dev][p.nt - 1].load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
+  if (p.lds > 64 * 1024 && !attr[dev].load(std::memory_order_acquire)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_run<MU, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
       return MOPA_ERR_LAUNCH;
-    attr[dev][p.nt - 1].store(true, std::memory_order_release);
+    attr[dev].store(true, std::memory_order_release);
   }
-  k<<<(unsigned)p.npieces, 512, p.lds, st>>>(hdr, ia, ib, K, p.S, A, ldA, cin, B, ldB, cout, p.sA, p.sB, slabs);
+  k_wgrad_run<MU, NT><<<(unsigned)p.npieces, 512, p.lds, st>>>(hdr, ia, ib, K, p.S, A, ldA, cin, B, ldB, cout, p.sA, p.sB, slabs);
   return hipGetLastError() == hipSuccess ? MOPA_OK : MOPA_ERR_LAUNCH;
 }
 
-// dweight[K][cin][cout] (+= if accumulate) from in[*, cin] and dout[*, cout] over the rules of the table the run-major rulebook `runs` was
-// built from (num_out = its output rows).  swap == 0: `in` rows are the rules' input rows and `dout` rows their output rows; swap == 1
-// (the stride-2 convolution's gradient on its deconvolution table: one_rule_per_row): the other way round.  ws >=
-// mopa_spconv_wgrad_run_workspace_bytes.  Rows 16-byte aligned (ld % 4 == 0).
+// dweight[K][cin][cout] (+= if accumulate & 1) from in[*, cin] and dout[*, cout] over the rules of the table the run-major rulebook `runs`
+// was built from (num_out = its output rows).  swap == 0: `in` rows are the rules' input rows and `dout` rows their output rows; swap == 1
+// (the stride-2 convolution's gradient on its deconvolution table: one_rule_per_row): the other way round.  accumulate bits 8-30: see
+// sprun_pack.h.  ws >= what mopa_spconv_wgrad_kernel reports for the same arguments (without a stated size:
+// mopa_spconv_wgrad_run_workspace_bytes).  Rows 16-byte aligned (ld % 4 == 0).
 MOPA_API int mopa_spconv_bwd_weight_run(const int32_t* runs, int32_t K, int32_t num_out, int32_t one_rule_per_row, int32_t swap, const float* in,
                                         int32_t ld_in, int32_t cin, const float* dout, int32_t ld_dout, int32_t cout, float* dweight,
                                         int32_t accumulate, void* ws, size_t ws_bytes, void* stream) {
   WgrPlan p;
-  if (!runs || !in || !dout || !dweight || num_out <= 0 || !wgr_plan(K, num_out, cin, cout, one_rule_per_row, &p)) return MOPA_ERR_ARG;
-  if (ld_in < cin || ld_dout < cout || (ld_in & 3) || (ld_dout & 3) || (((uintptr_t)in | (uintptr_t)dout | (uintptr_t)ws) & 15)) return MOPA_ERR_ARG;
-  if (!ws || ws_bytes < mopa_spconv_wgrad_run_workspace_bytes(K, num_out, cin, cout, one_rule_per_row)) return MOPA_ERR_WORKSPACE;
+  if (!runs || !in || !dout || !dweight) return MOPA_ERR_ARG;
+  const unsigned ptr_low = (unsigned)((uintptr_t)in & 15) | (unsigned)((uintptr_t)dout & 15) << 4 | (unsigned)((uintptr_t)ws & 15) << 8;
+  const int prc = wgr_pick(K, num_out, spk_stated_rows(accumulate, num_out), cin, cout, one_rule_per_row, ld_in, ld_dout, ptr_low, &p);
+  if (prc) return prc;
+  if (!ws || ws_bytes < wgr_ws_bytes(p, cin, cout)) return MOPA_ERR_WORKSPACE;
+  accumulate &= 1;
   hipStream_t st = (hipStream_t)stream;
   const int64_t cap = run_cap(K, num_out);
   const int* hdr = runs;
@@ -826,11 +850,13 @@ MOPA_API int mopa_spconv_bwd_weight_run(const int32_t* runs, int32_t K, int32_t 
   const int* ib = swap ? run_in : run_out;
   float* slabs = (float*)ws;
   int rc;
-  switch (p.mu) {
-    case 1: rc = launch_wgrad_run<1>(p, hdr, ia, ib, K, in, ld_in, cin, dout, ld_dout, cout, slabs, st); break;
-    case 2: rc = launch_wgrad_run<2>(p, hdr, ia, ib, K, in, ld_in, cin, dout, ld_dout, cout, slabs, st); break;
-    case 3: rc = launch_wgrad_run<3>(p, hdr, ia, ib, K, in, ld_in, cin, dout, ld_dout, cout, slabs, st); break;
-    default: rc = launch_wgrad_run<4>(p, hdr, ia, ib, K, in, ld_in, cin, dout, ld_dout, cout, slabs, st); break;
+  switch (p.pick) {
+#define WR(MU, N) case WGK(WGK_RUN, MU, N, 0, 0): rc = launch_wgrad_run<MU, N>(p, hdr, ia, ib, K, in, ld_in, cin, dout, ld_dout, cout, slabs, st); break;
+#define WRM(MU) WR(MU, 1) WR(MU, 2) WR(MU, 3) WR(MU, 4) WR(MU, 5) WR(MU, 6) WR(MU, 7)
+    WRM(1) WRM(2) WRM(3) WRM(4)
+#undef WRM
+#undef WR
+    default: return MOPA_ERR_ARG;
   }
   if (rc) return rc;
   const int n_e = cin * cout;

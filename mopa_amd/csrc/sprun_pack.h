@@ -65,3 +65,24 @@ static inline int spk_pick_run(int K, int64_t rows, int cin, int cout, int one_r
   const int rg = rules_est / 128 < 1024 ? 1 : 2;   // (fewer than ~4 items of 128 per CU: level 5 at 8 scans 27 -> 17 us with 64-slot items)
   return SPK(SPK_RUN, nt, 0, 0, 0) | (one_rule_per_row ? SPK_FLAG : 0) | rg << 24;
 }
+
+// ---- which kernel a weight-gradient launch runs (mopa_spconv_bwd_weight, mopa_spconv_bwd_weight_run), as ONE value: each entry point
+// computes it in one host function (pick_wgrad in spconv.hip / wgr_pick in sprun.hip) together with everything else of the launch
+// (chunks or pieces, workspace bytes, LDS bytes), launches through a switch over it, and mopa_spconv_wgrad_kernel returns it to a
+// caller that only asks.  Fields:
+//   bits 0-3   family (WGK_*)
+//   bits 4-7   MU: 16-channel blocks of Cin per wave (0: k_spconv_stem_wgrad)
+//   bits 8-11  NT: 16-column tiles of Cout
+//   bits 12-15 D: depth of the load ring (k_spconv_wgrad2)
+//   bits 16-18 NWV: waves per (offset, chunk) (k_spconv_wgrad2)
+enum { WGK_STEM = 1, WGK_SIMPLE = 2, WGK_PIPE = 3, WGK_RUN = 4 };
+#define WGK(fam, mu, nt, d, nwv) ((fam) | (mu) << 4 | (nt) << 8 | (d) << 12 | (nwv) << 16)
+// `accumulate` of the two entry points: bit 0 add to dweight, bits 8-30 "decide as if the table had this many 64-row tiles" (0: the
+// real row count) -- the convention of w_flip above (spk_stated_rows reads both).  The stated size moves the decisions that follow
+// the table's size alone (the wave target and the four-waves-per-block form of k_spconv_wgrad2, the piece size of k_wgrad_run); every
+// clamp and check (rows per chunk, slab caps, the bound on the slots, 32-bit row offsets, the workspace) stays on the real table.
+// What mopa_spconv_wgrad_kernel writes to its host array (int64): the plan behind the value above.
+enum { WGI_CHUNKS = 0, WGI_ROWS_PER_CHUNK = 1, WGI_S = 2, WGI_PIECES = 3, WGI_WS_BYTES = 4, WGI_LDS_BYTES = 5, WGI_BLOCKS = 6, WGI_N = 8 };
+// (sprun.hip) the run entry's decision for spconv.hip's query: the value above or the entry's error code; ptr_low as in the query
+int mopa_wgr_pick_for_query(int K, int64_t num_out, int64_t stated, int cin, int cout, int one_rule_per_row, int ld_in, int ld_dout,
+                            unsigned ptr_low, int64_t* info);
