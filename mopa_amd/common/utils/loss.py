@@ -304,3 +304,45 @@ def lovasz_softmax_logits(logits, labels, classes='present', ignore_index: int =
         raise ValueError(f"lovasz_softmax_logits: logits must be (P, C), not {tuple(logits.shape)}")
     offsets = [0, logits.shape[0]] if segments is None else [int(o) for o in segments]
     return _lovasz_call("lovasz_softmax_logits", logits, labels, True, offsets, ignore_index, classes)
+
+
+# -------------------------------------------------------------------------------------------------- l2_norm (csrc/supcon.hip)
+L2_NORM_MAX_FEATURES = 128
+
+
+class _L2Norm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        N, F = x.shape
+        y = torch.empty_like(x)
+        norm = torch.empty(N, dtype=torch.float32, device=x.device)
+        call("mopa_l2norm_rows_fwd", ptr(x), N, F, ptr(y), ptr(norm), stream())
+        ctx.save_for_backward(y, norm)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, norm = ctx.saved_tensors
+        dx = torch.empty_like(y)
+        call("mopa_l2norm_rows_bwd", ptr(y), ptr(norm), ptr(_f32c(g)), y.shape[0], y.shape[1], ptr(dx), stream())
+        return dx
+
+
+def l2_norm(feats: torch.Tensor) -> torch.Tensor:
+    """``feats / where(norm > 1e-8, norm, 1e-8)`` per row of ``feats (N, F)``, same call as ``mopa/common/utils/loss.py:230-238``, as
+    one wavefront-per-row kernel each way (csrc/supcon.hip; 1 <= F <= 128).  The squares are summed in float64 and the norm rounded
+    once to float32; the gradient is ``(g - y (y . g)) / norm`` where the norm is above 1e-8 and ``g / 1e-8`` where it is not (what
+    autograd gives through the reference's ``torch.where``).  float16 / bfloat16 inputs are cast to float32 and get their gradient in
+    their own dtype; the result is float32."""
+    if feats.dim() != 2:
+        raise ValueError(f"l2_norm: feats must be (N, F), not {tuple(feats.shape)}")
+    N, F = feats.shape
+    if not 1 <= F <= L2_NORM_MAX_FEATURES:
+        raise ValueError(f"l2_norm: feature width {F} is outside 1..{L2_NORM_MAX_FEATURES}")
+    if N == 0:
+        raise ValueError("l2_norm: no rows")
+    if not feats.is_floating_point():
+        raise TypeError("l2_norm: feats must be a floating-point tensor")
+    if not feats.is_cuda:
+        raise RuntimeError("l2_norm: feats is a CPU tensor; the hot path has no CPU fallback")
+    return _L2Norm.apply(feats.to(torch.float32).contiguous())

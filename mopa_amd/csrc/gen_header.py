@@ -77,6 +77,20 @@ SECTIONS = [
  * is not selected costs no sort work; no host read, no floating-point atomics: the same bits on every run.  `status` (int32 on the
  * device): bit 0 a label outside [0, C) that is not the ignore value (foreground for no class).  The arithmetic is stated in
  * DESIGN.md section 4; yardstick tests/_lovasz_reference.py, held against the reference's own float32 result."""),
+    ("supcon.hip", """Supervised contrastive loss on the device: SupConLoss of mopa/models/losses.py:123-184 (TRAIN.PC_MM.lambda_ctr_src /
+ * lambda_ctr_trg) and l2_norm of mopa/common/utils/loss.py:230-238, for float32 features of width 1 <= F <= 128 and int64 labels
+ * compared for equality only.  With S = A Q^T / T, per anchor m = max_j S, D = sum over negatives of (exp(S - m) + float32(1e-5)),
+ * loss = -mean_i ((1 / n_i) sum over positives of (S - m) - log D); no self-pair exclusion.  Nothing of size Na x Nq exists: the
+ * forward is one launch over (anchor tiles of 64) x (pool chunks) whose S tiles stay in the accumulators of v_mfma_f32_32x32x2_f32
+ * (features staged through LDS, odd widths zero padded there), with a running maximum and rescaled sums per row, and one finalize
+ * launch that merges the chunks in order and sums the rows in float64; the backward is one launch per side (anchors: side 0, pool:
+ * side 1) that recomputes the S tiles and multiplies W = [P] / n - [N] exp(S - m) / D on the same instruction, plus one ordered sum
+ * when the walk was split for occupancy.  The number of chunks depends on (Na, Nq) alone (mopa_supcon_pool_chunks); no
+ * floating-point atomics: the same bits on every run.  An anchor without a positive or without a negative is invalid: the loss is NaN
+ * and every gradient element NaN (skip_invalid = 0), or the row is left out of the mean (skip_invalid = 1; none valid: 0).
+ * `status` (int32 on the device, never read back by the call): bit 0 an anchor has no positive, bit 1 an anchor has no negative,
+ * bit 2 a non-finite S was met.  The arithmetic is stated in DESIGN.md section 4; yardstick tests/_supcon_reference.py, held against
+ * the reference's float64 autograd."""),
     ("pseudo.hip", """Pseudo-label update of the MoPA phase on the device (SURVEY 8f-3): EMA teacher (torch_ema update rule,
  * mopa/train/train_xmuda_mopa.py:221-226,587-591), entropy-weighted 2D/3D fusion (:282-291 with mopa/models/losses.py:10-19)
  * and the per-class median refinement (mopa/data/utils/refine_pseudo_labels.py:5-22), without host round trips."""),
